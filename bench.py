@@ -3,13 +3,14 @@
 
 One "step" = one pass of the hot path (prep -> candidates -> trellis -> back-trace, all on the GPU) over one batch of
 synthetic input that is already resident in HBM: BASELINE.json configs[2], 100 contigs x 1 Mbp of upper-case uniform-random
-DNA.  `value` (the headline) is WEAK scaling: every rank decodes its own 100 contigs per step.  The same run also times the
-STRONG-scaling form of config 3 as it is written (100 contigs in total, split over the ranks longest-first) and reports it
-under "strong"; and, at N = 1, the end-to-end rates of the drop-in ("e2e": host buffers -> augx_decode_batch -> paths ->
-genes -> GFF text; "cli": the augustus executable, FASTA file in, GFF out) and the reference's CPU path ("cpu_baseline").
+DNA.  `value` (the headline) is WEAK scaling: every rank decodes its own 100 contigs per step.  A plain run times those steps
+and nothing else.  With --full the same run also times the STRONG-scaling form of config 3 as it is written (100 contigs in
+total, split over the ranks longest-first) and reports it under "strong"; and, at N = 1, the end-to-end rates of the drop-in
+("e2e": host buffers -> augx_decode_batch -> paths -> genes -> GFF text; "cli": the augustus executable, FASTA file in, GFF
+out) and the reference's CPU path ("cpu_baseline").
 Contigs are independent: there is no data-path collective, ranks only meet in the barriers around the timed regions.
 
-Launch:  python bench.py [--gpus N --steps K --warmup W]
+Launch:  python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
   N > 1: one process per GPU.  Under torch.distributed.run (RANK/WORLD_SIZE in the environment) this process is one rank;
   started plainly with --gpus N > 1 it re-launches itself under torch.distributed.run with N ranks on 127.0.0.1.
 """
@@ -125,7 +126,7 @@ def parse_timing(stderr_text):
 def bounded_line(out, limit=LINE_LIMIT):
     """json.dumps(out) made to fit `limit` bytes: floats to 6 significant digits, then -- only while it is still too long -- the
     descriptive strings of the secondary legs go (longest first), then whole secondary legs (last added first).  The contract keys
-    (metric, value, ..., config, roofline, cpu_baseline) are never touched.  The untrimmed object goes to gpurun_out/bench_full.json."""
+    (metric, value, ..., config, roofline, cpu_baseline) are never touched.  The untrimmed object goes to --full-json PATH."""
     def rnd(x):
         if isinstance(x, float):
             return float("%.6g" % x)
@@ -184,6 +185,29 @@ def bounded_line(out, limit=LINE_LIMIT):
     line = json.dumps(out)
     assert len(line) < limit, "bench line of %d bytes" % len(line)
     return line
+
+
+DUMP_LIMIT = 60 << 20   # bytes of array data --dump-outputs writes at most (a seeded sample of the state rows beyond it)
+
+
+def dump_outputs(dirname, pieces):
+    """--dump-outputs: what the timed decode handed its caller, piece by piece in batch order, as float64 .npy files --
+    ln_viterbi, status, n_states (one value per piece) and states (one row per state of the paths: piece, begin, end, state, type).
+    Should the rows exceed DUMP_LIMIT, a fixed, seeded sample of them is kept, in path order."""
+    os.makedirs(dirname, exist_ok=True)
+    n_st = np.array([len(p.states) for p in pieces], dtype=np.int64)
+    arrays = {"ln_viterbi": np.array([p.ln_viterbi for p in pieces], dtype=np.float64),
+              "status": np.array([p.status for p in pieces], dtype=np.float64),
+              "n_states": n_st.astype(np.float64)}
+    rows = np.empty((int(n_st.sum()), 5), dtype=np.float64)
+    rows[:, 0] = np.repeat(np.arange(len(pieces)), n_st)
+    rows[:, 1:] = np.array([s for p in pieces for s in p.states], dtype=np.float64).reshape(-1, 4)
+    room = (DUMP_LIMIT - sum(x.nbytes for x in arrays.values())) // (rows.itemsize * rows.shape[1])
+    if len(rows) > room:
+        rows = rows[np.sort(np.random.default_rng(SEED0).choice(len(rows), size=room, replace=False))]
+    arrays["states"] = rows
+    for name, x in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), x)
 
 
 def cpu_model_string():
@@ -702,7 +726,17 @@ def main():
     ap.add_argument("--no-utr", action="store_true", help="skip the --UTR=on leg (the 71-state model, BASELINE config 4's trellis)")
     ap.add_argument("--utr-contigs", type=int, default=256)
     ap.add_argument("--utr-contig-len", type=int, default=160000)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary legs (two resident batches, strong scaling, e2e / gc_steps / cli / cli_sampled, the "
+                         "reference's CPU path, the --UTR=on model, the product's executable on the BASELINE shapes; the --no-* switches "
+                         "leave some out).  Without it the run times the headline steps and nothing else")
+    ap.add_argument("--full-json", metavar="PATH", help="with --full: the untrimmed result object to PATH (the printed line is bounded)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last decode of the timed batch(es) gave its caller (ln Viterbi, status "
+                         "and state path of every piece) as DIR/<name>.npy, float64")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # started plainly: become N ranks, one per GPU (the driver normally launches torch.distributed.run itself)
@@ -792,10 +826,10 @@ def main():
         run_steps(a.steps, True)         # EXACTLY --steps steps
         sync_all(decs)
         dt = max_over_ranks(time.perf_counter() - t0, dist)
-        for b in batches:                # sanity: the decode produced feasible paths
-            assert all(r.status == 0 for r in b.paths()), "decode failed"
+        pieces = [r for b in batches for r in b.paths()]   # what the last decode of each resident batch gave its caller
+        assert all(r.status == 0 for r in pieces), "decode failed"   # sanity: the decode produced feasible paths
         bases_rank = [sum(b.lens) for b in batches]
-        info = {"dt": dt, "n_fl": len(batches), "bases_per_step_rank": bases_rank[0] if bases_rank else 0,
+        info = {"dt": dt, "n_fl": len(batches), "bases_per_step_rank": bases_rank[0] if bases_rank else 0, "pieces": pieces,
                 "trellis_ms": float(np.mean(ms["trellis"])) if ms["trellis"] else 0.0,
                 "prep_ms": float(np.mean(ms["prep"])) if ms["prep"] else 0.0, "back_ms": float(np.mean(ms["back"])) if ms["back"] else 0.0}
         for b in batches:
@@ -806,11 +840,13 @@ def main():
 
     bases = a.contigs * a.contig_len
     weak = timed_phase("weak", a.inflight)
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, weak["pieces"])
     two = None
-    if world == 1 and a.inflight == 1 and not a.no_two_batches and a.steps >= 2:
+    if a.full and world == 1 and a.inflight == 1 and not a.no_two_batches and a.steps >= 2:
         two = timed_phase("weak", 2)   # (reported beside the headline: round 1's configuration, 2 x the HBM footprint)
     strong = None
-    if world > 1 and not a.no_strong:
+    if a.full and world > 1 and not a.no_strong:
         strong = timed_phase("strong", a.inflight)
     if rank == 0:
         ms_per_step = weak["dt"] / a.steps * 1e3
@@ -862,21 +898,18 @@ def main():
                              "workload": "BASELINE config 3 as written: the same %d contigs x %d bp in total, split longest-first over %d ranks"
                                          % (a.contigs, a.contig_len, world), "bases_per_step_rank0": strong["bases_per_step_rank"],
                              "trellis_ms": strong["trellis_ms"], "prep_ms": strong["prep_ms"]}
-        if world == 1:
+        if a.full and world == 1:
             if not a.no_e2e:
                 out.update(e2e_legs(cfg, model, local, rank_contigs("weak", 0, 1, a.contigs, a.contig_len)))
             if not a.no_cpu_baseline:  # the reference's CPU path, timed beside it (rank 0, N = 1 only)
                 out["cpu_baseline"] = cpu_baseline(cfg, a.cpu_sample_bp, a.cpu_host_sample_bp)
             if not a.no_utr:
                 out["utr"] = utr_leg(cfg, local, a)
-        if not a.no_product:  # (rank 0 drives every device from one process, as the executable does; the other ranks wait in the barrier)
+        if a.full and not a.no_product:  # (rank 0 drives every device from one process, as the executable does; the other ranks wait in the barrier)
             out["product"] = product_leg(cfg, a, world)
-        try:  # the whole object, untrimmed, beside the line (gpurun_out/ is merged back from the GPU box)
-            os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-            with open(os.path.join(ROOT, "gpurun_out", "bench_full.json"), "w") as fh:
+        if a.full and a.full_json:  # the whole object, untrimmed, beside the line
+            with open(a.full_json, "w") as fh:
                 json.dump(out, fh, indent=1)
-        except OSError:
-            pass
         print(bounded_line(out))
     if dist is not None:
         dist.barrier()

@@ -1,7 +1,10 @@
-"""bench.py's JSON line must fit the driver's 8 KB tail (round 3 printed 34 KB: 175 AUGX_TIMING strings, BENCH_r03.parsed = null)."""
+"""bench.py's JSON line must fit the driver's 8 KB tail (round 3 printed 34 KB: 175 AUGX_TIMING strings, BENCH_r03.parsed = null);
+what --dump-outputs writes."""
 import json
 import os
 import sys
+
+import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -46,3 +49,31 @@ def test_line_is_bounded_and_keeps_the_contract_keys():
 def test_a_short_line_is_left_alone():
     out = {"metric": "m", "value": 1.5, "leg": {"region": "r" * 300}}
     assert json.loads(bench.bounded_line(out)) == out
+
+
+class _Piece:
+    def __init__(self, status, lnv, states):
+        self.status, self.ln_viterbi, self.states = status, lnv, states
+
+
+def test_dump_outputs_writes_what_the_caller_got(tmp_path):
+    pieces = [_Piece(0, -1234.5678901234, [(0, 99, 0, 0), (100, 250, 3, 1)]), _Piece(0, -17.25, []), _Piece(0, -3.0, [(0, 9, 1, 2)])]
+    bench.dump_outputs(str(tmp_path), pieces)
+    got = {f.stem: np.load(f) for f in tmp_path.iterdir()}
+    assert sorted(got) == ["ln_viterbi", "n_states", "states", "status"]
+    assert all(x.dtype == np.float64 for x in got.values())
+    assert got["ln_viterbi"].tolist() == [-1234.5678901234, -17.25, -3.0]
+    assert got["n_states"].tolist() == [2, 0, 1] and got["status"].tolist() == [0, 0, 0]
+    assert got["states"].tolist() == [[0, 0, 99, 0, 0], [0, 100, 250, 3, 1], [2, 0, 9, 1, 2]]
+
+
+def test_dump_outputs_samples_rows_beyond_the_limit(tmp_path, monkeypatch):
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 40 * 100 + 3 * 8 * 2)
+    pieces = [_Piece(0, -1.0, [(i, i, 0, 0) for i in range(300)]), _Piece(0, -2.0, [(i, i, 1, 0) for i in range(200)])]
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), pieces)
+    rows = np.load(tmp_path / "a" / "states.npy")
+    assert rows.shape == (100, 5) and (rows == np.load(tmp_path / "b" / "states.npy")).all()   # the same seeded sample
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) < 40 * 100 + 3 * 8 * 2 + 4 * 256
+    key = rows[:, 0] * 1000 + rows[:, 1]
+    assert (np.diff(key) > 0).all()   # in path order
