@@ -581,6 +581,34 @@ void devFree(augx_decoder *d, void *p) {
     d->pooledBytes += it->second;
     d->live.erase(it);
 }
+// A buffer of the decoder's pool, given back to it when its owner goes.  Whoever drops or replaces one while kernels or copies
+// queued earlier may still touch it synchronises the stream first (or keeps it: the batch's `bufs`).
+struct DevBuf {
+    augx_decoder *d = nullptr;
+    void *p = nullptr;
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : d(o.d), p(o.p) { o.p = nullptr; }
+    ~DevBuf() { reset(); }
+    void reset() { devFree(d, p); p = nullptr; }
+    explicit operator bool() const { return p != nullptr; }
+    template <class T> T *as() const { return (T *)p; }
+    // Every pool allocation: what the buffer held goes back first, then it takes `bytes` from the pool of `dec`.  On failure the HIP
+    // error is cleared and `what` is the message: AUGX_E_NOMEM when the device is full, AUGX_E_HIP otherwise.
+    // AUGX_FAIL_ALLOC=<text> (tests of the way out of a failed allocation; read at every call): an allocation whose description
+    // contains the text fails as if the device were full, and the runtime is not asked.
+    int alloc(augx_decoder *dec, size_t bytes, const std::string &what) {
+        reset();
+        d = dec;
+        const char *fail = getenv("AUGX_FAIL_ALLOC");
+        const hipError_t e = fail && *fail && what.find(fail) != std::string::npos ? hipErrorOutOfMemory : devMalloc(d, &p, bytes);
+        if (e == hipSuccess) return AUGX_OK;
+        (void)hipGetLastError();
+        p = nullptr;
+        if (e == hipErrorOutOfMemory) { setLastError(what); return AUGX_E_NOMEM; }
+        setLastError(std::string("HIP error: ") + hipGetErrorString(e) + " (" + what + ")");
+        return AUGX_E_HIP;
+    }
+};
 } // namespace
 
 
@@ -590,20 +618,20 @@ struct augx_batch {
     BatchLayout L;
     BatchView V;               // device pointers
     BatchView *dV = nullptr;   // device copy of V (kernels with high register pressure take it by pointer)
-    std::vector<void *> bufs;
+    std::vector<DevBuf> bufs;  // buffers kept until the batch goes: the arrays of augx_batch_create, scan totals, the forward matrix
     int32_t *blkMinMax = nullptr; // [N/256][2] window-class range of every 256 slots
     int32_t *stairInfo = nullptr; // [2] kStairs: most planes of a piece, pieces left to the host
     int nPlAlloc = 0;          // planes the class-dependent arrays are allocated for (0: not yet)
     int64_t listCapAlloc = 0;  // entries per plane the candidate-list arrays are allocated for
     bool listsReady = false;   // the list offsets of this batch's pieces have been computed (its first decode)
     int64_t *dListOffs = nullptr;
-    void *planeBufs[NARR] = {};  // (ensureArrays)
+    DevBuf planeBufs[NARR];    // (ensureArrays)
     bool utrScanned = false;   // (dense) the UTR prefix scan of the current decode has run already (first decode: before the lists are sized)
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr}; // start, prep done, trellis done, backtrace done
     hipEvent_t evFwd = nullptr; // forward matrix complete (the sampler waits for this, not for what the stream got after it)
     uint64_t nItems = 0, nPairs = 0;
-    void *itemBuf = nullptr; // candidate buffer, sized per decode (kept while large enough)
-    void *udBuf = nullptr;   // (dense, UTR) descriptor buffer, sized like the candidate buffer
+    DevBuf itemBuf;          // candidate buffer, sized per decode (kept while large enough)
+    DevBuf udBuf;            // (dense, UTR) descriptor buffer, sized like the candidate buffer
     uint64_t nDescs = 0;
     bool decoded = false;
     bool itemsVerified = false; // the candidate buffer in use has held all candidates of this batch once
@@ -611,32 +639,20 @@ struct augx_batch {
     int chunkTotPlanes = 1;  // planes the scan totals are allocated for
     std::vector<int64_t> hListOffs; // host copy of the list offsets (first entry of every piece in the list arrays)
     bool memoReplayed = false; // the site values of this decode have been rebuilt from the reference's tssProbsPlus / aSSProb caches already
-    void *laSwBuf = nullptr;   // (dense, UTR) acceptor sites whose value changes during the sweep (BatchView::laSw)
+    DevBuf laSwBuf;            // (dense, UTR) acceptor sites whose value changes during the sweep (BatchView::laSw)
     size_t nLaSw = 0;          // its entries
     std::vector<std::shared_ptr<augx::dev::AssMemoReplay>> memoOf; // [piece] the aSSProb memo as the sweep left it (the sampler goes on from a copy), or null
 };
 
 namespace {
 
-template <class T> int devAlloc(augx_batch *b, T **ptr, int64_t count) {
-    void *p = nullptr;
-    const hipError_t e = devMalloc(b->dec, &p, (size_t)(count > 0 ? count : 1) * sizeof(T));
-    if (e == hipErrorOutOfMemory) {
-        (void)hipGetLastError();
-        setLastError("augx: out of device memory while allocating a batch; decode fewer bases per batch");
-        return AUGX_E_NOMEM;
-    }
-    HIP_TRY(e);
-    b->bufs.push_back(p);
-    *ptr = (T *)p;
-    return 0;
-}
-
 // Arrays whose size is only known at decode time: the class-dependent arrays ([nPl][...], see BatchView: one plane when the
 // batch is created, more when a piece turns out to have several GC classes) and the candidate-list arrays (sized from the
-// counted sites).  Re-allocated, larger, when a decode needs more planes or entries than the batch has.
-int ensureArrays(augx_batch *b, int nPl, int64_t listCap) {
+// counted sites).  Re-allocated, larger, when a decode needs more planes or entries than the batch has (grown: some were; the
+// device copy of V is then out of date).
+int ensureArrays(augx_batch *b, int nPl, int64_t listCap, bool *grown = nullptr) {
     if (nPl <= b->nPlAlloc && listCap <= b->listCapAlloc) return 0;
+    if (grown) *grown = true;
     if (nPl < b->nPlAlloc) nPl = b->nPlAlloc;
     if (listCap < b->listCapAlloc) listCap = b->listCapAlloc;
     BatchView &V = b->V;
@@ -658,21 +674,16 @@ int ensureArrays(augx_batch *b, int nPl, int64_t listCap) {
         {(void **)&V.tfSite, sizeof(USite), b->dec->dense ? LC : 1, 1}, {(void **)&V.laSite, sizeof(USite), b->dec->dense ? LC : 1, 1},
         {(void **)&V.fsSite, sizeof(USite), b->dec->dense ? LC : 1, 1}, {(void **)&V.lrSite, sizeof(USite), b->dec->dense ? LC : 1, 1},
         {(void **)&V.tmSite, sizeof(USite), b->dec->dense ? LC : 1, 1}, {(void **)&V.rtSite, sizeof(USite), b->dec->dense ? LC : 1, 1}};
+    const std::string what = "augx: out of device memory for the candidate-list / per-GC-class arrays (" + std::to_string(nPl) + " classes in one piece); decode fewer bases per batch";
     for (int i = 0; i < NARR; i++) {
         const bool isN = i < 2; // (fx, plsR: sized by the slots, they only grow with the planes)
         if (isN && nPl == b->nPlAlloc && b->planeBufs[i]) continue;
-        if (b->planeBufs[i]) { devFree(b->dec, b->planeBufs[i]); b->planeBufs[i] = nullptr; *slots[i].field = nullptr; }
-        void *p = nullptr;
-        if (devMalloc(b->dec, &p, (size_t)slots[i].planes * (size_t)slots[i].count * slots[i].elem) != hipSuccess) {
-            (void)hipGetLastError();
+        if (const int rc = b->planeBufs[i].alloc(b->dec, (size_t)slots[i].planes * (size_t)slots[i].count * slots[i].elem, what)) {
             b->nPlAlloc = 0; b->listCapAlloc = 0;
-            for (int k = 0; k < NARR; k++)
-                if (b->planeBufs[k]) { devFree(b->dec, b->planeBufs[k]); b->planeBufs[k] = nullptr; }
-            setLastError("augx: out of device memory for the candidate-list / per-GC-class arrays (" + std::to_string(nPl) + " classes in one piece); decode fewer bases per batch");
-            return AUGX_E_NOMEM;
+            for (int k = 0; k < NARR; k++) { b->planeBufs[k].reset(); *slots[k].field = nullptr; }
+            return rc;
         }
-        b->planeBufs[i] = p;
-        *slots[i].field = p;
+        *slots[i].field = b->planeBufs[i].p;
     }
     b->nPlAlloc = nPl;
     b->listCapAlloc = listCap;
@@ -804,16 +815,10 @@ void augx_decoder_destroy(augx_decoder *d) {
 void augx_batch_destroy(augx_batch *b) {
     if (!b) return;
     (void)hipSetDevice(b->dec->device);
-    for (void *p : b->bufs) devFree(b->dec, p);
-    for (void *p : b->planeBufs)
-        if (p) devFree(b->dec, p);
-    if (b->itemBuf) devFree(b->dec, b->itemBuf);
-    if (b->udBuf) devFree(b->dec, b->udBuf);
-    if (b->laSwBuf) devFree(b->dec, b->laSwBuf);
     for (auto &e : b->ev)
         if (e) (void)hipEventDestroy(e);
     if (b->evFwd) (void)hipEventDestroy(b->evFwd);
-    delete b;
+    delete b; // (its buffers go back to the decoder's pool)
 }
 
 // ---- the TSS window that begins at base 0 of a piece (include/augx.h: augx_tss0, augx_tss0_override; dense.h: k1UtrSignals)
@@ -858,13 +863,12 @@ int augx_batch_create(augx_decoder *d, const augx_piece *pieces, int n, augx_bat
     if (!d || !pieces || n < 1 || !out) { setLastError("augx_batch_create: bad argument"); return AUGX_E_ARG; }
     *out = nullptr;
     HIP_TRY(hipSetDevice(d->device));
-    augx_batch *b = new augx_batch();
+    std::unique_ptr<augx_batch, void (*)(augx_batch *)> b(new augx_batch(), augx_batch_destroy); // (any return below: the batch goes with all it holds)
     b->dec = d;
     try {
         b->L.build(pieces, n);
     } catch (std::exception &ex) {
         setLastError(ex.what());
-        delete b;
         return AUGX_E_ARG;
     }
     const BatchLayout &L = b->L;
@@ -873,44 +877,50 @@ int augx_batch_create(augx_decoder *d, const augx_piece *pieces, int n, augx_bat
     memset(&V, 0, sizeof V);
     V.nPieces = n; V.N = L.N; V.nChunks = L.nChunks;
     int rc = 0;
-#define DA(field, T, count) do { T *_p = nullptr; rc = devAlloc(b, &_p, (count)); if (rc) { augx_batch_destroy(b); return rc; } field = _p; } while (0)
-    int64_t *dOff; int32_t *dLen, *dIk, *dTk, *dCp; char *dRaw;
-    DA(dOff, int64_t, n + 1); DA(dLen, int32_t, n); DA(dIk, int32_t, n); DA(dTk, int32_t, n); DA(dCp, int32_t, L.nChunks);
-    DA(dRaw, char, Z.N);
+    auto keep = [&](auto *&field, int64_t count) { // a buffer the batch keeps; after a failure (rc) nothing more is allocated
+        using T = std::remove_pointer_t<std::decay_t<decltype(field)>>;
+        if (rc) return;
+        b->bufs.emplace_back();
+        rc = b->bufs.back().alloc(d, (size_t)(count > 0 ? count : 1) * sizeof(T), "augx: out of device memory while allocating a batch; decode fewer bases per batch");
+        field = b->bufs.back().as<T>();
+    };
+    int64_t *dOff = nullptr; int32_t *dLen = nullptr, *dIk = nullptr, *dTk = nullptr, *dCp = nullptr; char *dRaw = nullptr;
+    keep(dOff, n + 1); keep(dLen, n); keep(dIk, n); keep(dTk, n); keep(dCp, L.nChunks);
+    keep(dRaw, Z.N);
     V.off = dOff; V.len = dLen; V.initKind = dIk; V.termKind = dTk; V.chunkPiece = dCp; V.raw = dRaw;
-    DA(V.cls, int32_t, n); DA(V.clsMinMax, int32_t, 2 * n);
-    DA(b->blkMinMax, int32_t, (Z.N / 256 + 1) * 2);
-    DA(b->stairInfo, int32_t, 2);
-    DA(V.nPlanes, int32_t, n); DA(V.planeCls, int32_t, (int64_t)n * MAXPL);
-    DA(V.gcRaw, uint8_t, Z.N); DA(V.gcPlane, uint8_t, Z.N);
+    keep(V.cls, n); keep(V.clsMinMax, 2 * n);
+    keep(b->blkMinMax, (Z.N / 256 + 1) * 2);
+    keep(b->stairInfo, 2);
+    keep(V.nPlanes, n); keep(V.planeCls, (int64_t)n * MAXPL);
+    keep(V.gcRaw, Z.N); keep(V.gcPlane, Z.N);
     V.nPl = 1; V.listCap = 0; // (the list arrays are sized by the first decode, from the counted sites)
-    DA(V.code, uint8_t, Z.N);
-    DA(V.cnt, uint32_t, Z.N * NCNT);
-    DA(V.nsm, uint32_t, Z.N * 6);
-    DA(V.sig, double, Z.N * NSIG);
-    DA(V.gate, uint64_t, Z.N);
-    DA(V.site, int32_t, Z.N * NSITE);
-    DA(V.chunkTot, uint64_t, Z.N / SCAN_T * NFX);
+    keep(V.code, Z.N);
+    keep(V.cnt, Z.N * NCNT);
+    keep(V.nsm, Z.N * 6);
+    keep(V.sig, Z.N * NSIG);
+    keep(V.gate, Z.N);
+    keep(V.site, Z.N * NSITE);
+    keep(V.chunkTot, Z.N / SCAN_T * NFX);
     if (!d->dense) {
-        DA(V.bp, uint16_t, Z.N * SP);
-        DA(V.bpChain, uint8_t, Z.N * 8);
+        keep(V.bp, Z.N * SP);
+        keep(V.bpChain, Z.N * 8);
     } else {
-        DA(V.bpD, uint8_t, Z.N * d->hostT.S);
-        DA(V.ufx, uint64_t, Z.N * NUFX); DA(V.ucnt, uint32_t, Z.N * NUCNT); DA(V.usig, double, Z.N * NUSIG);
+        keep(V.bpD, Z.N * d->hostT.S);
+        keep(V.ufx, Z.N * NUFX); keep(V.ucnt, Z.N * NUCNT); keep(V.usig, Z.N * NUSIG);
     }
-    if (d->debugCells || d->dense) DA(V.cells, double, Z.N * d->hostT.S);
-    if (d->countNearTies) DA(V.nearTie, int32_t, n);
-    if (getenv("AUGX_PROF")) { DA(V.prof, uint64_t, (int64_t)n * 56 + 64); if (hipMemset(V.prof, 0, ((size_t)n * 56 + 64) * 8) != hipSuccess) { augx_batch_destroy(b); setLastError("augx_batch_create: hipMemset failed"); return AUGX_E_HIP; } }
-    if (!d->dense) { DA(V.vig, double, Z.N); DA(V.longV, double, Z.N * 6); }
-    DA(V.listCnt, int32_t, n); DA(b->dListOffs, int64_t, n + 1);
+    if (d->debugCells || d->dense) keep(V.cells, Z.N * d->hostT.S);
+    if (d->countNearTies) keep(V.nearTie, n);
+    if (getenv("AUGX_PROF")) { keep(V.prof, (int64_t)n * 56 + 64); if (!rc && hipMemset(V.prof, 0, ((size_t)n * 56 + 64) * 8) != hipSuccess) { setLastError("augx_batch_create: hipMemset failed"); return AUGX_E_HIP; } }
+    if (!d->dense) { keep(V.vig, Z.N); keep(V.longV, Z.N * 6); }
+    keep(V.listCnt, n); keep(b->dListOffs, n + 1);
     V.listOffs = b->dListOffs;
-    if ((rc = ensureArrays(b, 1, 0))) { augx_batch_destroy(b); return rc; }
+    if (rc || (rc = ensureArrays(b.get(), 1, 0))) return rc;
     V.blk = d->blk;
     V.nBlk = Z.N / V.blk;
-    DA(V.blkCnt, uint32_t, V.nBlk * 2); DA(V.blkSplit, uint32_t, V.nBlk * 3); DA(V.blkOff, uint64_t, V.nBlk * 2);
-    DA(V.candAlloc, CandAlloc, 1);
-    if (d->dense && d->hostT.utr) { DA(V.udOff, uint64_t, V.nBlk); DA(V.udCnt, uint32_t, V.nBlk); }
-    DA(V.lnv, double, n); DA(V.status, int32_t, n); DA(V.finalState, int32_t, n); DA(V.pathCount, int32_t, n);
+    keep(V.blkCnt, V.nBlk * 2); keep(V.blkSplit, V.nBlk * 3); keep(V.blkOff, V.nBlk * 2);
+    keep(V.candAlloc, 1);
+    if (d->dense && d->hostT.utr) { keep(V.udOff, V.nBlk); keep(V.udCnt, V.nBlk); }
+    keep(V.lnv, n); keep(V.status, n); keep(V.finalState, n); keep(V.pathCount, n);
     {   // pieces whose TSS window at base 0 is answered from an earlier sequence (augx_tss0_override)
         std::vector<double> v;
         {
@@ -925,27 +935,28 @@ int augx_batch_create(augx_decoder *d, const augx_piece *pieces, int n, augx_bat
         }
         if (!v.empty()) {
             double *dv = nullptr;
-            DA(dv, double, (int64_t)n * 2);
-            if (hipMemcpy(dv, v.data(), sizeof(double) * v.size(), hipMemcpyHostToDevice) != hipSuccess) { augx_batch_destroy(b); setLastError("augx_batch_create: upload failed"); return AUGX_E_HIP; }
+            keep(dv, (int64_t)n * 2);
+            if (rc) return rc;
+            if (hipMemcpy(dv, v.data(), sizeof(double) * v.size(), hipMemcpyHostToDevice) != hipSuccess) { setLastError("augx_batch_create: upload failed"); return AUGX_E_HIP; }
             V.tss0 = dv;
         }
     }
-    DA(V.pathRec, int32_t, Z.pathCap * 3);
+    keep(V.pathRec, Z.pathCap * 3);
     // segments of the trellis: enough workgroups for every compute unit, none shorter than what a fix-up needs
     b->plan = planSegments(L, d->model->m.t, d->nCU / d->share > 0 ? d->nCU / d->share : 1, d->dense ? -1 : 0); // (dense kernels: one workgroup per piece)
-    SegDesc *dSegs; int32_t *dSeg0;
+    SegDesc *dSegs = nullptr; int32_t *dSeg0 = nullptr;
     const int nSegs = (int)b->plan.segs.size();
-    DA(dSegs, SegDesc, nSegs); DA(dSeg0, int32_t, n + 1);
+    keep(dSegs, nSegs); keep(dSeg0, n + 1);
     V.nSegs = nSegs; V.segs = dSegs; V.pieceSeg0 = dSeg0; V.segCheckTiles = b->plan.checkTiles;
     if (const char *e = getenv("AUGX_SEG_CHECK_TILES")) V.segCheckTiles = atoi(e); // (tests of the give-up path: an unreachable check length)
-    DA(V.segStop, int32_t, nSegs); DA(V.segStatus, int32_t, nSegs); DA(V.segD, double, nSegs); DA(V.brkPos, int32_t, nSegs); DA(V.brkOff, double, nSegs);
-    DA(V.segStop2, int32_t, nSegs); DA(V.segD2, double, nSegs); DA(V.pieceCovered, int32_t, n);
+    keep(V.segStop, nSegs); keep(V.segStatus, nSegs); keep(V.segD, nSegs); keep(V.brkPos, nSegs); keep(V.brkOff, nSegs);
+    keep(V.segStop2, nSegs); keep(V.segD2, nSegs); keep(V.pieceCovered, n);
     if (b->plan.cut()) {
-        DA(V.ckRing, double, (int64_t)nSegs * 2 * WAVE * SP); DA(V.ckCol, double, Z.N / WAVE * SP);
-        DA(V.tileMinEop, int32_t, Z.N / WAVE); DA(V.tileCross, int32_t, Z.N / WAVE);
+        keep(V.ckRing, (int64_t)nSegs * 2 * WAVE * SP); keep(V.ckCol, Z.N / WAVE * SP);
+        keep(V.tileMinEop, Z.N / WAVE); keep(V.tileCross, Z.N / WAVE);
     }
-#undef DA
-    rc = [&]() -> int { // (any failure below: the batch is destroyed with everything it owns)
+    keep(b->dV, 1);
+    if (rc) return rc;
     const double tAlloc = getenv("AUGX_TIMING") ? std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() : 0.0;
     HIP_TRY(hipMemcpy(dOff, L.off.data(), sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(dLen, L.len.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice));
@@ -958,15 +969,11 @@ int augx_batch_create(augx_decoder *d, const augx_piece *pieces, int n, augx_bat
     HIP_TRY(hipMemset(V.gcPlane, 0, (size_t)Z.N));
     for (int p = 0; p < n; p++)
         HIP_TRY(hipMemcpy(dRaw + L.off[p] + 1, pieces[p].seq, (size_t)L.len[p], hipMemcpyHostToDevice));
-    { void *pv = nullptr; HIP_TRY(devMalloc(d, &pv, sizeof(BatchView))); b->bufs.push_back(pv); b->dV = (BatchView *)pv; }
     HIP_TRY(hipMemcpy(b->dV, &V, sizeof(BatchView), hipMemcpyHostToDevice));
     for (auto &e : b->ev) HIP_TRY(hipEventCreate(&e));
     if (tAlloc > 0) fprintf(stderr, "augx timing:       batch created: uploads + events %.3f s after the allocations (hipMalloc calls of this decoder so far: %.3f s for %.1f GB)\n",
                             std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() - tAlloc, d->mallocSeconds, d->mallocBytes / 1e9);
-    return AUGX_OK;
-    }();
-    if (rc) { augx_batch_destroy(b); return rc; }
-    *out = b;
+    *out = b.release();
     return AUGX_OK;
 }
 
@@ -1056,25 +1063,22 @@ int augx_batch_decode(augx_decoder *d, augx_batch *b) {
             b->listsReady = true;
             changed = true;
         }
-        const void *fxBefore = W.fx;
+        bool grown = false;
         if (timingFirst) tf[2] = nowS();
-        if ((rc = ensureArrays(b, nPl, W.listCap))) return rc;
+        if ((rc = ensureArrays(b, nPl, W.listCap, &grown))) return rc;
         if (timingFirst) tf[3] = nowS();
-        if (changed || fxBefore != W.fx) {
+        if (changed || grown) {
             W.nPl = nPl;
             HIP_TRY(hipMemcpy(b->dV, &W, sizeof(BatchView), hipMemcpyHostToDevice));
         }
     }
     }
-    if (V.nPl > b->chunkTotPlanes) { // (one set of chunk totals per plane of the class-dependent arrays)
-        uint64_t *nt = nullptr;
-        if (devMalloc(d, (void **)&nt, sizeof(uint64_t) * (size_t)V.nPl * (V.N / SCAN_T) * NFX) != hipSuccess) {
-            (void)hipGetLastError();
-            setLastError("augx_batch_decode: out of device memory for the scan totals");
-            return AUGX_E_NOMEM;
-        }
-        b->bufs.push_back(nt);
-        b->V.chunkTot = nt;
+    if (V.nPl > b->chunkTotPlanes) { // (one set of chunk totals per plane of the class-dependent arrays; the batch keeps the old set:
+                                      //  kernels queued already may still read it)
+        DevBuf nt;
+        if ((rc = nt.alloc(d, sizeof(uint64_t) * (size_t)V.nPl * (V.N / SCAN_T) * NFX, "augx_batch_decode: out of device memory for the scan totals"))) return rc;
+        b->V.chunkTot = nt.as<uint64_t>();
+        b->bufs.push_back(std::move(nt));
         b->chunkTotPlanes = V.nPl;
     }
     if (d->dense && !b->utrScanned) utrScan();
@@ -1093,32 +1097,21 @@ int augx_batch_decode(augx_decoder *d, augx_batch *b) {
         if (b->itemBuf && b->nItems > 0 && (uint64_t)W.itemCap > b->nItems + b->nItems / 16 + 65536) {
             // a batch decoded again: its candidate count is known, give back what the first estimate took too much
             HIP_TRY(hipStreamSynchronize(st));
-            devFree(d, b->itemBuf);
-            b->itemBuf = nullptr;
+            b->itemBuf.reset();
             b->itemsVerified = false;
         }
         if (!b->itemBuf) { // first estimate: uniform-random DNA has 1.2 pairs and 15 candidates per base
             W.itemCap = b->nItems > 0 ? (int64_t)(b->nItems + b->nItems / 16 + 65536) : W.N * 18 + 65536;
-            if (devMalloc(d, &b->itemBuf, (size_t)W.itemCap * sizeof(Item)) != hipSuccess) {
-                (void)hipGetLastError();
-                b->itemBuf = nullptr;
-                setLastError("augx_batch_decode: out of device memory for the candidate buffer; decode fewer bases per batch");
-                return AUGX_E_NOMEM;
-            }
-            W.items = (Item *)b->itemBuf;
+            if ((rc = b->itemBuf.alloc(d, (size_t)W.itemCap * sizeof(Item), "augx_batch_decode: out of device memory for the candidate buffer; decode fewer bases per batch"))) return rc;
+            W.items = b->itemBuf.as<Item>();
             HIP_TRY(hipMemcpyAsync(b->dV, &W, sizeof(BatchView), hipMemcpyHostToDevice, st));
         }
         const bool utrDesc = d->dense && d->hostT.utr;
         if (utrDesc && !b->udBuf) { // descriptors of the UTR exon cells: uniform-random DNA has 0.35 per base with the human parameters
             W.udCap = b->nDescs > 0 ? (int64_t)(b->nDescs + 64) : W.N / 2 + 65536;
             if (const char *e = getenv("AUGX_UD_CAP")) { if (b->nDescs == 0) W.udCap = atol(e) > 0 ? atol(e) : 1; } // (tests: a first estimate that is too small)
-            if (devMalloc(d, &b->udBuf, (size_t)W.udCap * sizeof(UDesc)) != hipSuccess) {
-                (void)hipGetLastError();
-                b->udBuf = nullptr;
-                setLastError("augx_batch_decode: out of device memory for the UTR descriptors; decode fewer bases per batch");
-                return AUGX_E_NOMEM;
-            }
-            W.ud = (UDesc *)b->udBuf;
+            if ((rc = b->udBuf.alloc(d, (size_t)W.udCap * sizeof(UDesc), "augx_batch_decode: out of device memory for the UTR descriptors; decode fewer bases per batch"))) return rc;
+            W.ud = b->udBuf.as<UDesc>();
             HIP_TRY(hipMemcpyAsync(b->dV, &W, sizeof(BatchView), hipMemcpyHostToDevice, st));
         }
         // (steady: the batch has been decoded with this very buffer before -- the same sequences give the same candidates, no
@@ -1141,29 +1134,15 @@ int augx_batch_decode(augx_decoder *d, augx_batch *b) {
             const bool itemsFit = (int64_t)tot.items <= W.itemCap, descsFit = !utrDesc || (int64_t)tot.descs <= W.udCap;
             if (itemsFit && descsFit) { b->itemsVerified = true; break; }
             if (attempt > 0) { setLastError("augx_batch_decode: candidate buffers overflowed twice"); return AUGX_E_HIP; }
-            if (!itemsFit) {
-                devFree(d, b->itemBuf);
-                b->itemBuf = nullptr;
+            if (!itemsFit) { // (the stream is idle: the buffers may go)
                 W.itemCap = (int64_t)tot.items + 64;
-                if (devMalloc(d, &b->itemBuf, (size_t)W.itemCap * sizeof(Item)) != hipSuccess) {
-                    (void)hipGetLastError();
-                    b->itemBuf = nullptr;
-                    setLastError("augx_batch_decode: out of device memory for the candidate buffer (" + std::to_string(tot.items) + " candidates); decode fewer bases per batch");
-                    return AUGX_E_NOMEM;
-                }
-                W.items = (Item *)b->itemBuf;
+                if ((rc = b->itemBuf.alloc(d, (size_t)W.itemCap * sizeof(Item), "augx_batch_decode: out of device memory for the candidate buffer (" + std::to_string(tot.items) + " candidates); decode fewer bases per batch"))) return rc;
+                W.items = b->itemBuf.as<Item>();
             }
             if (!descsFit) {
-                devFree(d, b->udBuf);
-                b->udBuf = nullptr;
                 W.udCap = (int64_t)tot.descs + 64;
-                if (devMalloc(d, &b->udBuf, (size_t)W.udCap * sizeof(UDesc)) != hipSuccess) {
-                    (void)hipGetLastError();
-                    b->udBuf = nullptr;
-                    setLastError("augx_batch_decode: out of device memory for the UTR descriptors; decode fewer bases per batch");
-                    return AUGX_E_NOMEM;
-                }
-                W.ud = (UDesc *)b->udBuf;
+                if ((rc = b->udBuf.alloc(d, (size_t)W.udCap * sizeof(UDesc), "augx_batch_decode: out of device memory for the UTR descriptors; decode fewer bases per batch"))) return rc;
+                W.ud = b->udBuf.as<UDesc>();
             }
             HIP_TRY(hipMemcpyAsync(b->dV, &W, sizeof(BatchView), hipMemcpyHostToDevice, st));
         }
@@ -1373,15 +1352,12 @@ static int augx_batch_forward_launch(augx_decoder *d, augx_batch *b) {
     HIP_TRY(hipSetDevice(d->device));
     BatchView &W = b->V;
     if (!W.fwd) {
-        void *p = nullptr, *q = nullptr;
-        if (devMalloc(d, &p, sizeof(double) * (size_t)W.N * d->hostT.S) != hipSuccess || devMalloc(d, &q, sizeof(double) * (size_t)W.nPieces) != hipSuccess) {
-            (void)hipGetLastError();
-            if (p) devFree(d, p);
-            setLastError("augx_batch_forward: out of device memory for the forward matrix; decode fewer bases per batch");
-            return AUGX_E_NOMEM;
-        }
-        b->bufs.push_back(p); b->bufs.push_back(q);
-        W.fwd = (double *)p; W.lnFwd = (double *)q;
+        const char *what = "augx_batch_forward: out of device memory for the forward matrix; decode fewer bases per batch";
+        DevBuf p, q;
+        int rc = p.alloc(d, sizeof(double) * (size_t)W.N * d->hostT.S, what);
+        if (rc || (rc = q.alloc(d, sizeof(double) * (size_t)W.nPieces, what))) return rc;
+        W.fwd = p.as<double>(); W.lnFwd = q.as<double>();
+        b->bufs.push_back(std::move(p)); b->bufs.push_back(std::move(q));
         HIP_TRY(hipMemcpyAsync(b->dV, &W, sizeof(BatchView), hipMemcpyHostToDevice, d->stream));
     }
     if (d->dense) launchDense(d->blk, 1, false, (unsigned)W.nPieces, d->stream, d->dT, b->dV);
@@ -1413,6 +1389,10 @@ struct CopySlot {
     }
     ~CopySlot() { { std::lock_guard<std::mutex> lk(g_copyMu); g_copyFree++; } g_copyCv.notify_all(); }
 };
+// Waits for a stream on the way out of a scope.  Declared after the device buffers and host vectors that the work queued on the
+// stream touches, it runs before they go, on every return: an early one must not leave copies or kernels in flight into memory that
+// has been given back.  On the successful way out the stream is idle already.  (A null stream: nothing was queued asynchronously.)
+struct CopyDrain { hipStream_t s; ~CopyDrain() { if (s) (void)hipStreamSynchronize(s); } };
 }
 
 #include "snipmemo.h"
@@ -1464,6 +1444,7 @@ int snippetCacheReplay(augx_decoder *d, augx_batch *b, int64_t &nPatched, bool f
     auto fetch = [&](int p, PieceData &D) -> int {
         SnippetReplay &R = D.R;
         const hipStream_t fst = D.st; // (the piece's own stream: queued, waited for once)
+        CopyDrain drain{fst};         // (the copies land in D, which the worker frees when this fails)
         auto cp = [fst](void *dst, const void *src, size_t bytes) { return fst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, fst) : hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost); };
         const int len = b->L.len[p];
         const int64_t o = b->L.off[p];
@@ -1526,24 +1507,23 @@ int snippetCacheReplay(augx_decoder *d, augx_batch *b, int64_t &nPatched, bool f
             }
             if (DP->wins.empty()) return AUGX_OK;
             DP->poolAll.resize((size_t)pool + 1); DP->fxAll.resize((size_t)fx + 1); DP->FAll.resize((size_t)fr + 1);
-            void *dW = nullptr, *dI = nullptr, *dX = nullptr, *dF = nullptr;
-            auto freeAll = [&]() { if (dW) devFree(d, dW); if (dI) devFree(d, dI); if (dX) devFree(d, dX); if (dF) devFree(d, dF); };
-            if (devMalloc(d, &dW, sizeof(GatherWin) * DP->wins.size()) != hipSuccess || devMalloc(d, &dI, sizeof(Item) * ((size_t)pool + 1)) != hipSuccess ||
-                devMalloc(d, &dX, sizeof(uint64_t) * ((size_t)fx + 1)) != hipSuccess || (fr > 0 && devMalloc(d, &dF, sizeof(double) * ((size_t)fr + 1)) != hipSuccess)) {
-                (void)hipGetLastError();
-                freeAll();
-                return AUGX_E_NOMEM;
-            }
-            hipError_t e = hipMemcpyAsync(dW, DP->wins.data(), sizeof(GatherWin) * DP->wins.size(), hipMemcpyHostToDevice, cst);
+            DevBuf dW, dI, dX, dF;
+            CopyDrain drain{cst};
+            const char *what = "augx: out of device memory for a window of the snippet-cache replay";
+            int rc = dW.alloc(d, sizeof(GatherWin) * DP->wins.size(), what);
+            if (!rc) rc = dI.alloc(d, sizeof(Item) * ((size_t)pool + 1), what);
+            if (!rc) rc = dX.alloc(d, sizeof(uint64_t) * ((size_t)fx + 1), what);
+            if (!rc && fr > 0) rc = dF.alloc(d, sizeof(double) * ((size_t)fr + 1), what);
+            if (rc) return rc;
+            hipError_t e = hipMemcpyAsync(dW.p, DP->wins.data(), sizeof(GatherWin) * DP->wins.size(), hipMemcpyHostToDevice, cst);
             if (e == hipSuccess) {
-                hipLaunchKernelGGL(kGatherWindows, dim3((unsigned)DP->wins.size()), dim3(256), 0, cst, V, (const GatherWin *)dW, (Item *)dI, (uint64_t *)dX, fromLists ? nullptr : mat, (double *)dF, S);
+                hipLaunchKernelGGL(kGatherWindows, dim3((unsigned)DP->wins.size()), dim3(256), 0, cst, V, dW.as<const GatherWin>(), dI.as<Item>(), dX.as<uint64_t>(), fromLists ? nullptr : mat, dF.as<double>(), S);
                 e = hipGetLastError();
             }
-            if (e == hipSuccess && pool > 0) e = hipMemcpyAsync(DP->poolAll.data(), dI, sizeof(Item) * (size_t)pool, hipMemcpyDeviceToHost, cst);
-            if (e == hipSuccess && fx > 0) e = hipMemcpyAsync(DP->fxAll.data(), dX, sizeof(uint64_t) * (size_t)fx, hipMemcpyDeviceToHost, cst);
-            if (e == hipSuccess && fr > 0) e = hipMemcpyAsync(DP->FAll.data(), dF, sizeof(double) * (size_t)fr, hipMemcpyDeviceToHost, cst);
+            if (e == hipSuccess && pool > 0) e = hipMemcpyAsync(DP->poolAll.data(), dI.p, sizeof(Item) * (size_t)pool, hipMemcpyDeviceToHost, cst);
+            if (e == hipSuccess && fx > 0) e = hipMemcpyAsync(DP->fxAll.data(), dX.p, sizeof(uint64_t) * (size_t)fx, hipMemcpyDeviceToHost, cst);
+            if (e == hipSuccess && fr > 0) e = hipMemcpyAsync(DP->FAll.data(), dF.p, sizeof(double) * (size_t)fr, hipMemcpyDeviceToHost, cst);
             const hipError_t e2 = cst ? hipStreamSynchronize(cst) : hipDeviceSynchronize();
-            freeAll();
             if (e != hipSuccess || e2 != hipSuccess) { (void)hipGetLastError(); return AUGX_E_HIP; }
             return AUGX_OK;
         };
@@ -1617,19 +1597,15 @@ int snippetCacheReplay(augx_decoder *d, augx_batch *b, int64_t &nPatched, bool f
     nPatched = (int64_t)pIdx.size();
     if (timing) fprintf(stderr, "augx timing:       replay of %zu pieces: set up in %.3f s, tables fetched and windows replayed (%d pieces side by side) in %.3f s\n", todo.size(), tFetch, GROUP, tRun);
     if (pIdx.empty()) return AUGX_OK;
-    void *dIdx = nullptr, *dTe = nullptr;
-    if (devMalloc(d, &dIdx, sizeof(uint64_t) * pIdx.size()) != hipSuccess || devMalloc(d, &dTe, sizeof(double) * pTe.size()) != hipSuccess) {
-        (void)hipGetLastError();
-        if (dIdx) devFree(d, dIdx);
-        setLastError("augx_batch_forward: out of device memory");
-        return AUGX_E_NOMEM;
-    }
-    HIP_TRY(hipMemcpyAsync(dIdx, pIdx.data(), sizeof(uint64_t) * pIdx.size(), hipMemcpyHostToDevice, d->stream));
-    HIP_TRY(hipMemcpyAsync(dTe, pTe.data(), sizeof(double) * pTe.size(), hipMemcpyHostToDevice, d->stream));
-    hipLaunchKernelGGL(kPatchItems, dim3((unsigned)((pIdx.size() + 255) / 256)), dim3(256), 0, d->stream, V, (const uint64_t *)dIdx, (const double *)dTe, (int)pIdx.size());
+    DevBuf dIdx, dTe;
+    CopyDrain drain{d->stream}; // (the host vectors and the two buffers go when the stream is idle)
+    int rc = dIdx.alloc(d, sizeof(uint64_t) * pIdx.size(), "augx_batch_forward: out of device memory");
+    if (rc || (rc = dTe.alloc(d, sizeof(double) * pTe.size(), "augx_batch_forward: out of device memory"))) return rc;
+    HIP_TRY(hipMemcpyAsync(dIdx.p, pIdx.data(), sizeof(uint64_t) * pIdx.size(), hipMemcpyHostToDevice, d->stream));
+    HIP_TRY(hipMemcpyAsync(dTe.p, pTe.data(), sizeof(double) * pTe.size(), hipMemcpyHostToDevice, d->stream));
+    hipLaunchKernelGGL(kPatchItems, dim3((unsigned)((pIdx.size() + 255) / 256)), dim3(256), 0, d->stream, V, dIdx.as<const uint64_t>(), dTe.as<const double>(), (int)pIdx.size());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(d->stream)); // (the host vectors and the two buffers go away)
-    devFree(d, dIdx); devFree(d, dTe);
+    HIP_TRY(hipStreamSynchronize(d->stream));
     return AUGX_OK;
 }
 // UTR states on pieces with several GC classes: the forward TSS windows and the acceptor sites whose value the reference computed
@@ -1639,7 +1615,6 @@ int snippetCacheReplay(augx_decoder *d, augx_batch *b, int64_t &nPatched, bool f
 int utrCachesReplay(augx_decoder *d, augx_batch *b, const double *mat, bool &rebuilt) {
     rebuilt = false;
     if (b->memoReplayed || getenv("AUGX_NO_ASSMEMO")) return AUGX_OK;
-    b->memoReplayed = true;
     BatchView &W = b->V;
     const int n = W.nPieces;
     hipStream_t st = d->stream;
@@ -1653,7 +1628,7 @@ int utrCachesReplay(augx_decoder *d, augx_batch *b, const double *mat, bool &reb
     int64_t maxList = 0;
     for (int p = 0; p < n; p++)
         if (nPl[p] > 1) { todo.push_back(p); maxList = std::max(maxList, b->hListOffs[(size_t)p + 1] - b->hListOffs[(size_t)p]); }
-    if (todo.empty()) return AUGX_OK;
+    if (todo.empty()) { b->memoReplayed = true; return AUGX_OK; }
     AssMemoReplay proto;
     proto.T = &d->hostT;
     proto.requesters();
@@ -1661,28 +1636,31 @@ int utrCachesReplay(augx_decoder *d, augx_batch *b, const double *mat, bool &reb
     rq.n = proto.nReq;
     for (int r = 0; r < 8; r++) rq.s[r] = r < proto.nReq ? proto.reqS[r] : 0;
     const int64_t nSiteSlots = W.listCap + 8 * (int64_t)n + 8;
-    int32_t *dQ = nullptr, *dChanged = nullptr;
-    uint8_t *dAlive = nullptr, *dGate = nullptr;
-    std::vector<void *> tmp;
-    auto freeTmp = [&]() { for (void *q : tmp) devFree(d, q); tmp.clear(); };
-    auto grab = [&](void **ptr, size_t bytes) -> bool { if (devMalloc(d, ptr, bytes ? bytes : 1) != hipSuccess) { (void)hipGetLastError(); return false; } tmp.push_back(*ptr); return true; };
-    if (!grab((void **)&dQ, sizeof(int32_t) * (size_t)nSiteSlots) || !grab((void **)&dAlive, (size_t)nSiteSlots) || !grab((void **)&dGate, (size_t)W.N) || !grab((void **)&dChanged, sizeof(int32_t))) {
-        freeTmp();
-        setLastError("augx: out of device memory for the replay of the aSSProb memo");
-        return AUGX_E_NOMEM;
-    }
-    HIP_TRY(hipMemsetAsync(dChanged, 0, sizeof(int32_t), st));
-    const dim3 gridSites((unsigned)((maxList + 8 + 255) / 256), (unsigned)n);
-    hipLaunchKernelGGL(kTssReplay, gridSites, dim3(256), 0, st, d->dT, W, mat, dChanged);
-    hipLaunchKernelGGL(kMemoSites, gridSites, dim3(256), 0, st, d->dT, W, mat, rq, dQ, dAlive);
-    hipLaunchKernelGGL(kMemoGates, dim3((unsigned)((W.N + 255) / 256)), dim3(256), 0, st, d->dT, W, rq, dGate);
-    HIP_TRY(hipGetLastError());
-    // (only what the multi-class pieces own comes over)
+    // what the stream's copies and kernels touch, then the guard that waits for them on every way out (declared after it all)
     struct PieceIn { std::vector<int32_t> q; std::vector<uint8_t> alive; std::shared_ptr<AssMemoReplay> Rp; std::vector<AssPatch> pt; std::vector<AssSwIn> sw; int extras = 0; };
-    b->memoOf.assign((size_t)n, nullptr);
     std::vector<std::unique_ptr<PieceIn>> in;
     int32_t nTss = 0;
-    HIP_TRY(hipMemcpyAsync(&nTss, dChanged, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    std::vector<uint32_t> tmpc(todo.size());
+    std::vector<AssPatch> pt;
+    std::vector<int32_t> ptPiece;
+    std::vector<AssSwIn> sw;
+    DevBuf dQ, dAlive, dGate, dChanged, dPt, dPp, dSw;
+    CopyDrain drain{st};
+    const char *what = "augx: out of device memory for the replay of the aSSProb memo";
+    int rc = dQ.alloc(d, sizeof(int32_t) * (size_t)nSiteSlots, what);
+    if (!rc) rc = dAlive.alloc(d, (size_t)nSiteSlots, what);
+    if (!rc) rc = dGate.alloc(d, (size_t)W.N, what);
+    if (!rc) rc = dChanged.alloc(d, sizeof(int32_t), what);
+    if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(dChanged.p, 0, sizeof(int32_t), st));
+    const dim3 gridSites((unsigned)((maxList + 8 + 255) / 256), (unsigned)n);
+    hipLaunchKernelGGL(kTssReplay, gridSites, dim3(256), 0, st, d->dT, W, mat, dChanged.as<int32_t>());
+    hipLaunchKernelGGL(kMemoSites, gridSites, dim3(256), 0, st, d->dT, W, mat, rq, dQ.as<int32_t>(), dAlive.as<uint8_t>());
+    hipLaunchKernelGGL(kMemoGates, dim3((unsigned)((W.N + 255) / 256)), dim3(256), 0, st, d->dT, W, rq, dGate.as<uint8_t>());
+    HIP_TRY(hipGetLastError());
+    // (only what the multi-class pieces own comes over)
+    b->memoOf.assign((size_t)n, nullptr);
+    HIP_TRY(hipMemcpyAsync(&nTss, dChanged.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     for (int p : todo) {
         in.emplace_back(new PieceIn());
         PieceIn &I = *in.back();
@@ -1691,14 +1669,13 @@ int utrCachesReplay(augx_decoder *d, augx_batch *b, const double *mat, bool &reb
         I.Rp = std::make_shared<AssMemoReplay>();
         b->memoOf[(size_t)p] = I.Rp;
         I.q.resize((size_t)ns); I.alive.resize((size_t)ns); I.Rp->gateOwn.resize((size_t)len); I.Rp->planeOwn.resize((size_t)len);
-        HIP_TRY(hipMemcpyAsync(I.q.data(), dQ + s0, sizeof(int32_t) * (size_t)ns, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(I.alive.data(), dAlive + s0, (size_t)ns, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(I.Rp->gateOwn.data(), dGate + o + 1, (size_t)len, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(I.q.data(), dQ.as<int32_t>() + s0, sizeof(int32_t) * (size_t)ns, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(I.alive.data(), dAlive.as<uint8_t>() + s0, (size_t)ns, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(I.Rp->gateOwn.data(), dGate.as<uint8_t>() + o + 1, (size_t)len, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(I.Rp->planeOwn.data(), W.gcPlane + o + 1, (size_t)len, hipMemcpyDeviceToHost, st));
     }
     std::vector<int32_t> nLa((size_t)n, 0);
     {   // length of every piece's LA list: the count at its last slot
-        std::vector<uint32_t> tmpc((size_t)todo.size());
         for (size_t k = 0; k < todo.size(); k++)
             HIP_TRY(hipMemcpyAsync(&tmpc[k], W.cnt + fidx(b->L.off[todo[k]] + b->L.len[todo[k]], CNT_LA, NCNT), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
@@ -1727,9 +1704,6 @@ int utrCachesReplay(augx_decoder *d, augx_batch *b, const double *mat, bool &reb
         for (auto &t2 : th) t2.join();
     }
     const double t2 = timing ? now() : 0.0;
-    std::vector<AssPatch> pt;
-    std::vector<int32_t> ptPiece;
-    std::vector<AssSwIn> sw;
     long long calls = 0, flushes = 0, extras = 0;
     for (size_t k = 0; k < todo.size(); k++) {
         PieceIn &I = *in[k];
@@ -1738,23 +1712,19 @@ int utrCachesReplay(augx_decoder *d, augx_batch *b, const double *mat, bool &reb
         calls += I.Rp->calls; flushes += I.Rp->flushes; extras += I.extras;
     }
     if (!pt.empty()) {
-        AssPatch *dPt = nullptr; int32_t *dPp = nullptr; AssSwIn *dSw = nullptr;
-        if (b->laSwBuf) { devFree(d, b->laSwBuf); b->laSwBuf = nullptr; W.laSw = nullptr; b->nLaSw = 0; }
-        if (!grab((void **)&dPt, sizeof(AssPatch) * pt.size()) || !grab((void **)&dPp, sizeof(int32_t) * pt.size()) || !grab((void **)&dSw, sizeof(AssSwIn) * (sw.size() + 1)) ||
-            devMalloc(d, &b->laSwBuf, sizeof(LaSw) * (sw.size() + 1)) != hipSuccess) {
-            (void)hipGetLastError();
-            b->laSwBuf = nullptr;
-            freeTmp();
-            setLastError("augx: out of device memory for the replay of the aSSProb memo");
-            return AUGX_E_NOMEM;
-        }
-        HIP_TRY(hipMemcpyAsync(dPt, pt.data(), sizeof(AssPatch) * pt.size(), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(dPp, ptPiece.data(), sizeof(int32_t) * pt.size(), hipMemcpyHostToDevice, st));
-        if (!sw.empty()) HIP_TRY(hipMemcpyAsync(dSw, sw.data(), sizeof(AssSwIn) * sw.size(), hipMemcpyHostToDevice, st));
-        W.laSw = (const LaSw *)b->laSwBuf;
+        b->laSwBuf.reset(); W.laSw = nullptr; b->nLaSw = 0; // (the stream is idle)
+        rc = dPt.alloc(d, sizeof(AssPatch) * pt.size(), what);
+        if (!rc) rc = dPp.alloc(d, sizeof(int32_t) * pt.size(), what);
+        if (!rc) rc = dSw.alloc(d, sizeof(AssSwIn) * (sw.size() + 1), what);
+        if (!rc) rc = b->laSwBuf.alloc(d, sizeof(LaSw) * (sw.size() + 1), what);
+        if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(dPt.p, pt.data(), sizeof(AssPatch) * pt.size(), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(dPp.p, ptPiece.data(), sizeof(int32_t) * pt.size(), hipMemcpyHostToDevice, st));
+        if (!sw.empty()) HIP_TRY(hipMemcpyAsync(dSw.p, sw.data(), sizeof(AssSwIn) * sw.size(), hipMemcpyHostToDevice, st));
+        W.laSw = b->laSwBuf.as<const LaSw>();
         b->nLaSw = sw.size();
         HIP_TRY(hipMemcpyAsync(b->dV, &W, sizeof(BatchView), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(kAssPatch, dim3((unsigned)((pt.size() + 255) / 256)), dim3(256), 0, st, d->dT, W, dPt, dPp, (int)pt.size(), dSw, (LaSw *)b->laSwBuf);
+        hipLaunchKernelGGL(kAssPatch, dim3((unsigned)((pt.size() + 255) / 256)), dim3(256), 0, st, d->dT, W, dPt.as<AssPatch>(), dPp.as<int32_t>(), (int)pt.size(), dSw.as<AssSwIn>(), b->laSwBuf.as<LaSw>());
         HIP_TRY(hipGetLastError());
     }
     rebuilt = nTss > 0 || !pt.empty();
@@ -1763,8 +1733,8 @@ int utrCachesReplay(augx_decoder *d, augx_batch *b, const double *mat, bool &reb
         launchUtrDesc(d->blk, (unsigned)(W.N / (NT / 16)), st, d->dT, W);
         HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(hipStreamSynchronize(st)); // (the host vectors and the temporary buffers go away)
-    freeTmp();
+    HIP_TRY(hipStreamSynchronize(st));
+    b->memoReplayed = true;
     if (timing)
         fprintf(stderr, "augx timing:       UTR states, %zu pieces with several GC classes: %d TSS windows and %zu acceptor sites (%zu changes of value during the sweep; %lld past the end of a piece left) rebuilt from "
                         "the reference's caches; inputs gathered in %.3f s, %lld calls of the aSSProb memo walked (emptied %lld times) in %.3f s, values rebuilt in %.3f s\n",
@@ -1890,9 +1860,7 @@ int augx_batch_sample_prepare(augx_decoder *d, augx_batch *b, int piece, augx_sa
     }
     if (!H) H.reset(new augx_sample_prep());
     SamplePiece &P = H->P;
-    // (declared after H, so it runs BEFORE H is freed on every early return: copies still in flight on the non-blocking stream must
-    //  not land in host buffers that have been given back; on the way out of a successful call the stream is idle already)
-    struct CopyDrain { hipStream_t s; ~CopyDrain() { if (s) (void)hipStreamSynchronize(s); } } copyDrain{cst};
+    CopyDrain copyDrain{cst}; // (declared after H: runs before H is freed)
     {   // (an object that comes round: everything a piece sets only under a condition goes back to its default)
         P.plane.clear(); P.planeCls.clear(); P.uh.reset(); P.dense = false; P.hT = nullptr; P.hB = nullptr; P.hp = 0;
         P.memo = nullptr; P.memoOwner.reset(); P.vitPath.clear(); P.memoVitDiffs = 0;
@@ -2008,7 +1976,7 @@ int augx_batch_sample_prepare(augx_decoder *d, augx_batch *b, int piece, augx_sa
         }
         if (b->laSwBuf && b->nLaSw) { // (acceptor sites whose value changes during the sweep: the records index the batch's table)
             U.laSw.resize(b->nLaSw);
-            HIP_TRY(cp(U.laSw.data(), b->laSwBuf, sizeof(LaSw) * b->nLaSw));
+            HIP_TRY(cp(U.laSw.data(), b->laSwBuf.p, sizeof(LaSw) * b->nLaSw));
             HIP_TRY(flush());
         }
         BatchView &HB = U.B;

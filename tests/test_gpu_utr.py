@@ -171,6 +171,40 @@ def test_gpu_utr_descriptor_buffer_grows(monkeypatch):
             assert np.array_equal(b.cells(i), V), (rep, i)
 
 
+def test_gpu_utr_batch_decodes_again_after_the_memo_replay_ran_out_of_memory(monkeypatch):
+    """a decode whose replay of tssProbsPlus and the aSSProb memo cannot get its device buffers (AUGX_FAIL_ALLOC: the allocations of
+    that description fail as if the device were full) reports AUGX_E_NOMEM; the same batch decoded again replays the caches -- every
+    cell, score and path the twin's that runs them inside its loop.  On these records the replay changes cells (without it: others)."""
+    from test_emu import _multiclass_records
+    monkeypatch.setenv("AUGX_DEBUG_CELLS", "1")
+    monkeypatch.delenv("AUGX_EXACT_MULTICLASS", raising=False)
+    m = ax.Model(config_path(), "human", UTR="on", softmasking="0", sample="0")
+    d = ax.Decoder(m, 0)
+    byname = dict(golden_inputs())
+    recs = _multiclass_records(21)[:4] + [(k, byname[k].upper()) for k in ("multigc_gene", "multigc_two", "multigc_rand", "multigc_levels")]
+    seqs = [s for _, s in recs]
+    want = [twin_decode(m.tables_ptr, s, m.n_states, cells=True, cache=True) for s in seqs]
+    monkeypatch.setenv("AUGX_NO_ASSMEMO", "1")
+    plain = ax.Batch(d, seqs)
+    plain.decode()
+    assert sum(int(not np.array_equal(plain.cells(i), w[3])) for i, w in enumerate(want)) >= 2
+    monkeypatch.delenv("AUGX_NO_ASSMEMO")
+    b = ax.Batch(d, seqs)
+    monkeypatch.setenv("AUGX_FAIL_ALLOC", "aSSProb memo")
+    failed = None
+    try:  # (not pytest.raises: a traceback kept in this frame would hold the decoder and its batches in a reference cycle)
+        b.decode()
+    except ax.AugxError as e:
+        failed = (e.code, str(e))
+    assert failed is not None and failed[0] == ax.AUGX_E_NOMEM and "aSSProb memo" in failed[1], failed
+    monkeypatch.delenv("AUGX_FAIL_ALLOC")
+    b.decode()
+    for i, ((name, seq), w, r) in enumerate(zip(recs, want, b.paths())):
+        rc, lnv, path, V, gc = w
+        assert r.status == rc == 0 and r.ln_viterbi == lnv and r.states == path, name
+        assert np.array_equal(b.cells(i), V), name
+
+
 @needs_ref
 @pytest.mark.parametrize("seed", [11037, 11059, 11073, 11088])
 def test_cli_soak_seeds_with_utr_states_gc_steps_and_sampling(tmp_path, monkeypatch, seed):
