@@ -536,26 +536,45 @@ struct VarDesc { // 64 bytes (kind, frame and geometry of the state are per-stat
 };
 static_assert(sizeof(VarDesc) == 64, "VarDesc layout");
 
-// wave-level bookkeeping primitives (device: cross-lane instructions; emulator: loops over the lane arrays)
+// wave-level bookkeeping primitives (device: cross-lane instructions; emulator: loops over the lane arrays).  Every lane of the
+// wavefront takes part (the callers are not inside a divergent branch); lane `lane` of waveRead is the same for all lanes
 #ifdef AUGX_EMU
 inline void waveInclScan(int *v, int w) { for (int l = 1; l < WAVE; l++) v[w * WAVE + l] += v[w * WAVE + l - 1]; }
+inline void waveInclMax(int *v, int w) { for (int l = 1; l < WAVE; l++) v[w * WAVE + l] = v[w * WAVE + l - 1] > v[w * WAVE + l] ? v[w * WAVE + l - 1] : v[w * WAVE + l]; }
 inline int waveRead(const int *v, int w, int lane) { return v[w * WAVE + lane]; }
-#else
-__device__ inline void waveInclScan(int *v, int) {
-    int x = v[0];
-    const int lane = threadIdx.x & 63;
-    for (int o = 1; o < 64; o <<= 1) { int u = __shfl_up(x, o, 64); if (lane >= o) x += u; }
-    v[0] = x;
-}
-__device__ inline int waveRead(const int *v, int, int lane) { return __shfl(v[0], lane, 64); }
-#endif
-#ifdef AUGX_EMU
 inline int waveMin(const int *v, int w) { int m = v[w * WAVE]; for (int l = 1; l < WAVE; l++) m = v[w * WAVE + l] < m ? v[w * WAVE + l] : m; return m; }
 #else
-__device__ inline int waveMin(const int *v, int) {
-    int x = v[0];
-    for (int o = 32; o >= 1; o >>= 1) { const int y = __shfl_xor(x, o, 64); x = y < x ? y : x; }
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(__GFX9__)
+#error "the wave scans use the DPP row broadcasts (row_bcast:15 / row_bcast:31) that only gfx9 has"
+#endif
+// inclusive scan over the 64 lanes in the data-parallel-primitive form of the VALU moves (no trip through the LDS crossbar as
+// __shfl_up / __shfl_xor make): row_shr:1/2/4/8 inside the rows of 16 lanes, then row_bcast:15 into rows 1 and 3, row_bcast:31
+// into rows 2 and 3 (gfx9 DPP controls 0x111.., 0x142, 0x143).  A lane without a source keeps `id`, the identity of `op`
+template <int CTRL, int ROW_MASK, class T> __device__ inline T dppFrom(T id, T x) {
+    if constexpr (sizeof(T) == 8) {
+        const uint32_t lo = (uint32_t)dppMov<CTRL, ROW_MASK>((int)(uint32_t)id, (int)(uint32_t)x);
+        const uint32_t hi = (uint32_t)dppMov<CTRL, ROW_MASK>((int)(uint32_t)((uint64_t)id >> 32), (int)(uint32_t)((uint64_t)x >> 32));
+        return (T)(((uint64_t)hi << 32) | lo);
+    } else return (T)dppMov<CTRL, ROW_MASK>((int)id, (int)x);
+}
+template <class T, class OP> __device__ inline T waveScanWith(T x, T id, OP op) {
+    x = op(x, dppFrom<0x111, 0xf>(id, x));
+    x = op(x, dppFrom<0x112, 0xf>(id, x));
+    x = op(x, dppFrom<0x114, 0xf>(id, x));
+    x = op(x, dppFrom<0x118, 0xf>(id, x));
+    x = op(x, dppFrom<0x142, 0xa>(id, x));
+    x = op(x, dppFrom<0x143, 0xc>(id, x));
     return x;
+}
+// sums, or maxima of unsigned values (identity 0), of 64-bit fields (the prefix scans of decoder.hip)
+template <bool SUM> __device__ inline uint64_t waveScanIncl(uint64_t x) {
+    return waveScanWith<uint64_t>(x, 0, [](uint64_t a, uint64_t b) -> uint64_t { return SUM ? a + b : (a > b ? a : b); });
+}
+__device__ inline void waveInclScan(int *v, int) { v[0] = waveScanWith<int>(v[0], 0, [](int a, int b) { return a + b; }); }
+__device__ inline void waveInclMax(int *v, int) { v[0] = waveScanWith<int>(v[0], -2147483647 - 1, [](int a, int b) { return a > b ? a : b; }); }
+__device__ inline int waveRead(const int *v, int, int lane) { return __builtin_amdgcn_readlane(v[0], lane); }
+__device__ inline int waveMin(const int *v, int) {
+    return __builtin_amdgcn_readlane(waveScanWith<int>(v[0], 2147483647, [](int a, int b) { return a < b ? a : b; }), 63);
 }
 #endif
 AUGX_HD int popc64(uint64_t x) { return __builtin_popcountll(x); }
@@ -601,12 +620,15 @@ struct CandLds {
     VarConst vc[SP];
     VarDesc desc[NWAVES][DCAP];                          // per wavefront (= tile): descriptors of its (base, state) pairs
     uint8_t pairJ[NWAVES][WAVE], pairS[NWAVES][WAVE];    // the pairs of the current round: base offset in the tile, state
-    int scan[NWAVES][3][WAVE];                           // inclusive lane scans of the pair counts of the three groups
+    int scan[NWAVES][3][WAVE];                           // inclusive lane scans of the pair counts of the three groups; in pass 2 per pair
+                                                         // of the round: [0] its first candidate in the store order, [1] / [2] in the
+                                                         // numbering of its class (short introns / exon states)
     uint32_t cntItems[NWAVES][MAXNB], cntNonRT[NWAVES][MAXNB]; // per block: candidates (then: first candidate), candidates but RTERMINAL
     unsigned long long baseW[NWAVES][2];                 // first pair / first candidate of the tile in the batch's buffers
     uint8_t codes[NWAVES * WAVE + 2 * WAVE];             // the bases of the workgroup's tiles and 64 to either side (Piece::lcode)
-    uint16_t queue[NWAVES][2][2 * WAVE];                 // candidates of the current round waiting to be evaluated with their kind: [0] exon
-                                                         // states, [1] those that need the general formula (index in the round)
+    int8_t head[NWAVES][WAVE];                           // per chunk of 64 candidates of a class: the pair whose first candidate in the
+                                                         // chunk is at this lane (-1: none)
+    uint32_t slowQ[NWAVES][2 * WAVE];                    // exon candidates of the round that need the general formula (number in class E)
 };
 
 // read-only view of one piece for the candidate kernel (everything comes from HBM / L2)
@@ -1110,6 +1132,11 @@ AUGX_KFN void candTile(const CandCtx &X, CandLds &L, int w, int j0, int64_t gblk
     }
 #endif
     // ---- pass 2: evaluate and store
+    // A round's candidates are evaluated class by class: first those of the short introns (87 %, a short code path with one 16-byte
+    // load), then those of the exon states (long paths with a dozen dependent loads), each class 64 candidates at a time, so that a
+    // wavefront runs one code path with its lanes full.  Each candidate is stored at its place in the tile's order all the same
+    // (first candidate of its pair in that order + its index).  The 2 % of exon candidates that need the general emission formula
+    // (thousands of cycles) queue up and are evaluated a wavefront full at a time.
     uint32_t itemsDone = 0;
     TV(int, mnEop); // smallest predecessor position of a live candidate of the tile (BatchView::tileMinEop)
     FOR_WLANES(t, w) { TX(mnEop) = 0x7fffffff; }
@@ -1118,126 +1145,109 @@ AUGX_KFN void candTile(const CandCtx &X, CandLds &L, int w, int j0, int64_t gblk
         const int nPr = totalPairs - r0 < WAVE ? totalPairs - r0 : WAVE;
         // descriptor slot of pair r0 + q: the first DCAP pairs kept theirs, later ones are described again into the slots
         // of pairs already done
-        TV(int, tot);
+        TV(int, tot); TV(int, totA); TV(int, totE); // candidates of the lane's pair: all, of class A (short intron), of class E (exon)
+        TV(int, inc); TV(int, incA); TV(int, incE);
         FOR_WLANES(t, w) {
             const int l = t & 63;
-            TX(tot) = 0;
+            TX(tot) = 0; TX(totA) = 0;
             if (l < nPr) {
                 if (r0 + l >= DCAP) varDescribe<MULTI, DENSE>(X, L.pairS[w][l], j0 + L.pairJ[w][l], L.desc[w][l]);
                 TX(tot) = L.desc[w][r0 + l < DCAP ? r0 + l : l].total;
+                if ((maskLess >> L.pairS[w][l]) & 1) TX(totA) = TX(tot);
             }
+            TX(totE) = TX(tot) - TX(totA);
+            TX(inc) = TX(tot); TX(incA) = TX(totA); TX(incE) = TX(totE);
+            L.head[w][l] = -1;
+        }
+        waveInclScan(inc, w); waveInclScan(incA, w); waveInclScan(incE, w);
+        const int nA = waveRead(incA, w, WAVE - 1), nE = waveRead(incE, w, WAVE - 1);
+        FOR_WLANES(t, w) {
+            const int l = t & 63;
+            L.scan[w][0][l] = TX(inc) - TX(tot); L.scan[w][1][l] = TX(incA) - TX(totA); L.scan[w][2][l] = TX(incE) - TX(totE);
         }
         WAVE_SYNC();
-        TV(int, ibase); // inclusive prefix of the candidate counts
-        FOR_WLANES(t, w) { TX(ibase) = TX(tot); }
-        waveInclScan(ibase, w);
-        const int totalItems = waveRead(ibase, w, WAVE - 1);
-        // (the scan rows are free by now: row 0 takes the prefix, padded, for the candidates' search of their pair)
-        FOR_WLANES(t, w) { const int l = t & 63; L.scan[w][0][l] = l < nPr ? TX(ibase) : 0x7fffffff; }
-        WAVE_SYNC();
-        // A chunk of 64 consecutive candidates mixes kinds: short-intron candidates (87 %, a short code path with one 16-byte
-        // load) and, in small clusters at the end of every block, exon candidates (long paths with a dozen dependent loads), 2 %
-        // of which need the general emission formula (thousands of cycles).  Evaluating a mixed chunk in place runs every path
-        // with a few live lanes each.  So: short introns are evaluated in place, exon candidates queue up and are evaluated a
-        // wavefront at a time, and from there the few that need the general formula queue up once more.
-        int nQ[2] = {0, 0};               // (uniform) queued candidates of this round
-        const bool canQueue = totalItems < 65536;
-        // candidate `it` of the round by the lane of thread t; mode: 0 everything, 1 short introns only, 2 exon states (fast
-        // formulas) only.  Returns true if the candidate needs the general formula (mode 2) and was not stored
-        auto evalStore = [&](auto modeC, int t, int it, int q, int first) -> bool {
+        // the pair of candidate base + lane of class c (1 A, 2 E) for every lane, without a search: each pair with candidates in
+        // [base, base + 64) writes its lane at the lane of the first of them, an inclusive max-scan hands it on to the lanes after
+        auto pairsOf = [&](int c, const int *cnt, int base, int *q) {
+            FOR_WLANES(t, w) {
+                const int l = t & 63, f = L.scan[w][c][l], e = f + cnt[TI];
+                if (cnt[TI] > 0 && f < base + WAVE && e > base) L.head[w][(f > base ? f : base) - base] = (int8_t)l;
+            }
+            WAVE_SYNC();
+            FOR_WLANES(t, w) { const int l = t & 63; q[TI] = L.head[w][l]; L.head[w][l] = -1; } // (cleared for the next chunk)
+            waveInclMax(q, w);
+            WAVE_SYNC();
+        };
+        // candidate idx of pair q of the round by the lane of thread t; mode: 0 every kind, 1 short introns only, 2 exon states
+        // (fast formulas) only.  Returns true if the candidate needs the general formula (mode 2) and was not stored
+        auto evalStore = [&](auto modeC, int t, int q, int idx) -> bool {
             constexpr int MODE = decltype(modeC)::value;
             const int dj = L.pairJ[w][q], s2 = L.pairS[w][q];
             double te; int key; uint32_t src;
             bool needSlow;
-            varEvalItem<MULTI, MODE == 2, MODE, DENSE>(X, s2, j0 + dj, L.desc[w][r0 + q < DCAP ? r0 + q : q], it - first, te, key, src, needSlow);
+            varEvalItem<MULTI, MODE == 2, MODE, DENSE>(X, s2, j0 + dj, L.desc[w][r0 + q < DCAP ? r0 + q : q], idx, te, key, src, needSlow);
             if (needSlow) return true;
             if (key < 0 || !(te > AUGX_NINF)) { te = AUGX_NINF; key = 0; }
             else if (key - KEY_BIAS < TX(mnEop)) TX(mnEop) = key - KEY_BIAS;
             Item I;
             // (the pair id carries the state: 6 bits of it while S <= 64, 7 in the records of the dense kernels)
             I.te = te; I.kp = ((uint32_t)(DENSE ? (((dj % BLK) << 7) | X.vc[s2].state) : (((dj % BLK) << 6) | s2)) << KEY_BITS) | ((uint32_t)key & KEY_MASK); I.src = src;
-            B.items[itemBase + itemsDone + it] = I;
+            B.items[itemBase + itemsDone + (uint32_t)L.scan[w][0][q] + (uint32_t)idx] = I;
             return false;
         };
-        auto pairOf = [&](int it, int &first) -> int { // the pair of candidate `it`: the number of pairs that end at or before it
-            int pos = 0;
-#pragma unroll
-            for (int step = WAVE / 2; step >= 1; step >>= 1)
-                if (L.scan[w][0][pos + step - 1] <= it) pos += step;
-            first = pos > 0 ? L.scan[w][0][pos - 1] : 0;
-            return pos;
-        };
-        auto push = [&](int qi, int *flag, int *itv) { // lanes with flag: their candidate joins queue qi, in lane order
-            TV(int, inc);
-            FOR_WLANES(t, w) { TX(inc) = flag[TI]; }
-            waveInclScan(inc, w);
-            const int nNew = waveRead(inc, w, WAVE - 1);
-            if (nNew > 0) {
-                FOR_WLANES(t, w) { if (flag[TI]) L.queue[w][qi][nQ[qi] + TX(inc) - 1] = (uint16_t)itv[TI]; }
-                nQ[qi] += nNew;
-                WAVE_SYNC();
+        // class A: short introns, in place
+        for (int base = 0; base < nA; base += WAVE) {
+            TV(int, q);
+            pairsOf(1, totA, base, q);
+            FOR_WLANES(t, w) {
+                const int it = base + (t & 63);
+                if (it < nA) { const int qq = q[TI]; evalStore(std::integral_constant<int, 1>{}, t, qq, it - L.scan[w][1][qq]); }
             }
-        };
-        auto drop = [&](int qi, int cnt) { // the first cnt entries of queue qi are done: the rest moves to the front
-            TV(int, mv);
-            FOR_WLANES(t, w) { const int l = t & 63; TX(mv) = cnt + l < nQ[qi] ? (int)L.queue[w][qi][cnt + l] : -1; }
-            WAVE_SYNC();
-            FOR_WLANES(t, w) { const int l = t & 63; if (TX(mv) >= 0) L.queue[w][qi][l] = (uint16_t)TX(mv); }
-            WAVE_SYNC();
-            nQ[qi] -= cnt;
-        };
+        }
+        // class E: exon states; the candidates that need the general formula join the slow queue, in lane order
+        int nS = 0; // (uniform) queued candidates of this round
         auto flushSlow = [&](int cnt) {
             FOR_WLANES(t, w) {
                 const int l = t & 63;
-                if (l < cnt) {
-                    const int it = (int)L.queue[w][1][l];
-                    int first;
-                    const int q = pairOf(it, first);
-                    evalStore(std::integral_constant<int, 0>{}, t, it, q, first);
+                if (l < cnt) { // (the queue holds the candidate's number in class E: its pair is the last one that starts at or before it)
+                    const int it = (int)L.slowQ[w][l];
+                    int q = 0;
+#pragma unroll
+                    for (int step = WAVE / 2; step >= 1; step >>= 1)
+                        if (L.scan[w][2][q + step] <= it) q += step;
+                    evalStore(std::integral_constant<int, 0>{}, t, q, it - L.scan[w][2][q]);
                 }
             }
             WAVE_SYNC();
-            drop(1, cnt);
+            TV(int, mv); // the rest moves to the front
+            FOR_WLANES(t, w) { const int l = t & 63; TX(mv) = cnt + l < nS ? (int)L.slowQ[w][cnt + l] : -1; }
+            WAVE_SYNC();
+            FOR_WLANES(t, w) { const int l = t & 63; if (TX(mv) >= 0) L.slowQ[w][l] = (uint32_t)TX(mv); }
+            WAVE_SYNC();
+            nS -= cnt;
         };
-        auto flushExon = [&](int cnt) {
-            TV(int, slow); TV(int, itv);
+        for (int base = 0; base < nE; base += WAVE) {
+            TV(int, q); TV(int, slow);
+            pairsOf(2, totE, base, q);
             FOR_WLANES(t, w) {
-                const int l = t & 63;
-                TX(slow) = 0; TX(itv) = 0;
-                if (l < cnt) {
-                    const int it = (int)L.queue[w][0][l];
-                    int first;
-                    const int q = pairOf(it, first);
-                    TX(itv) = it;
-                    TX(slow) = evalStore(std::integral_constant<int, 2>{}, t, it, q, first);
-                }
-            }
-            WAVE_SYNC();
-            drop(0, cnt);
-            push(1, slow, itv);
-            if (nQ[1] >= WAVE) flushSlow(WAVE);
-        };
-        for (int base = 0; base < totalItems; base += WAVE) {
-            TV(int, exon); TV(int, itv);
-            FOR_WLANES(t, w) { // one candidate per lane
                 const int it = base + (t & 63);
-                TX(exon) = 0; TX(itv) = it;
-                if (it < totalItems) {
-                    int first;
-                    const int q = pairOf(it, first);
-                    const int kind = X.vc[L.pairS[w][q]].kind;
-                    if (!canQueue) evalStore(std::integral_constant<int, 0>{}, t, it, q, first);
-                    else if (kind == AUGX_K_LESSD || kind == AUGX_K_RLESSD) evalStore(std::integral_constant<int, 1>{}, t, it, q, first);
-                    else TX(exon) = 1;
-                }
+                TX(slow) = 0;
+                if (it < nE) { const int qq = q[TI]; TX(slow) = evalStore(std::integral_constant<int, 2>{}, t, qq, it - L.scan[w][2][qq]); }
             }
-            push(0, exon, itv);
-            if (nQ[0] >= WAVE) flushExon(WAVE);
+            TV(int, sinc);
+            FOR_WLANES(t, w) { TX(sinc) = TX(slow); }
+            waveInclScan(sinc, w);
+            const int nNew = waveRead(sinc, w, WAVE - 1);
+            if (nNew > 0) {
+                FOR_WLANES(t, w) { if (TX(slow)) L.slowQ[w][nS + TX(sinc) - 1] = (uint32_t)(base + (t & 63)); }
+                nS += nNew;
+                WAVE_SYNC();
+                if (nS >= WAVE) flushSlow(WAVE);
+            }
         }
-        if (nQ[0] > 0) flushExon(nQ[0]);
-        if (nQ[1] > 0) flushSlow(nQ[1]);
+        if (nS > 0) flushSlow(nS);
         WAVE_SYNC();
-        itemsDone += (uint32_t)totalItems;
+        itemsDone += (uint32_t)(nA + nE);
     }
     if (B.tileMinEop) { // (batches with cut pieces: the fix-ups of the trellis size their check window by it)
         const int m = waveMin(mnEop, w);
