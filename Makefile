@@ -61,7 +61,7 @@ oracle: oracle/libghmm_twin.so
 oracle/libghmm_twin.so: oracle/ghmm_twin.cc include/augx.h
 	$(CXX) $(CXXFLAGS) -shared -o $@ oracle/ghmm_twin.cc
 
-emu: build/libaugx_emu.so build/libaugx_emu_pl1.so
+emu: build/libaugx_emu.so build/libaugx_emu_pl1.so build/libaugx_emu_slowq.so
 build/libaugx_emu.so: tests/emu/emu.cc $(DEVHDR) include/augx.h
 	@mkdir -p build
 	$(CXX) $(CXXFLAGS) -shared -o $@ tests/emu/emu.cc
@@ -70,6 +70,11 @@ build/libaugx_emu.so: tests/emu/emu.cc $(DEVHDR) include/augx.h
 build/libaugx_emu_pl1.so: tests/emu/emu.cc $(DEVHDR) include/augx.h
 	@mkdir -p build
 	$(CXX) $(CXXFLAGS) -DAUGX_MAXPL_LDS=1 -shared -o $@ tests/emu/emu.cc
+# the same emulator with a slow-queue threshold of 5 (kernels.h: SLOWQ_AT): candTile then flushes its queue of exon candidates that
+# need the general formula before it is full, and moves the rest to the front, on ordinary inputs
+build/libaugx_emu_slowq.so: tests/emu/emu.cc $(DEVHDR) include/augx.h
+	@mkdir -p build
+	$(CXX) $(CXXFLAGS) -DAUGX_SLOWQ_AT=5 -shared -o $@ tests/emu/emu.cc
 
 ref:
 	$(MAKE) -C oracle -j8

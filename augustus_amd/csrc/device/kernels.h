@@ -518,6 +518,24 @@ AUGX_HD void k1SiteConsts(const DevTables &T, const BatchView &B, int64_t g, int
 static long long g_emuJumpProbes = 0, g_emuJumps = 0, g_emuQuietChecks = 0;
 static long long g_emuQuietTiles = 0, g_emuJumpTiles = 0; // tiles the trellis took as chain-only tiles / jumped over in a run of N (trellisPiece)
 static long long g_emuSlowA = 0, g_emuSlowB = 0, g_emuSlowVig = 0, g_emuSlowList = 0, g_emuSlowWaves = 0, g_emuItemWaves = 0; // emulator statistics: candidates taking the general evaluation path
+// branches of candTile's pass 2 that the emulated tiles took (tests/test_emu_cand.py: the inputs must reach every one of them)
+enum EmuCand {
+    EC_TILES,             // tiles that reached pass 2
+    EC_TILES_GT_WAVE,     //   with more than WAVE pairs (several rounds)
+    EC_TILES_GT_DCAP,     //   with more than DCAP pairs (descriptors written again into used slots)
+    EC_ROUNDS_A_GT_WAVE,  // rounds with more than WAVE short-intron candidates (several class-A chunks)
+    EC_ROUNDS_E_GT_WAVE,  // rounds with more than WAVE exon candidates (several class-E chunks)
+    EC_ROUNDS_A0,         // rounds without a short-intron candidate
+    EC_ROUNDS_E0,         // rounds without an exon candidate
+    EC_CHUNKS_A_CONT,     // class-A chunks in which a pair continues from the chunk before (a head at lane 0 with f < base)
+    EC_CHUNKS_E_CONT,     // the same for class E
+    EC_FULL_FLUSH,        // flushes of the slow queue at the threshold (SLOWQ_AT)
+    EC_FULL_FLUSH_MOVE,   //   that left entries to move to the front
+    EC_TAIL_FLUSH,        // flushes of the rest of the queue at the end of a round
+    EC_MAX_NS,            // largest fill of the slow queue (a maximum, not a count)
+    EC_N
+};
+static long long g_emuCand[EC_N] = {0};
 #endif
 struct VarDesc { // 64 bytes (kind, frame and geometry of the state are per-state constants: VarConst)
     int8_t pl;              // plane (GC class) of the end base j: selects every class-dependent array
@@ -616,6 +634,13 @@ AUGX_HD void fillVarConst(const DevTables &T, const BatchView &B, int p, int l, 
 #define AUGX_DCAP 96
 #endif
 constexpr int DCAP = AUGX_DCAP; // descriptors of a tile that stay in LDS between the counting and the emitting pass (>= WAVE)
+#ifndef AUGX_SLOWQ_AT
+#define AUGX_SLOWQ_AT WAVE
+#endif
+// fill of the slow queue of candTile at which a wavefront full of it is evaluated (lower values: a test build of the emulator, which
+// then takes that branch and the move of the rest to the front on ordinary inputs)
+constexpr int SLOWQ_AT = AUGX_SLOWQ_AT;
+static_assert(SLOWQ_AT >= 1 && SLOWQ_AT <= WAVE, "slow queue threshold");
 struct CandLds {
     VarConst vc[SP];
     VarDesc desc[NWAVES][DCAP];                          // per wavefront (= tile): descriptors of its (base, state) pairs
@@ -1140,6 +1165,9 @@ AUGX_KFN void candTile(const CandCtx &X, CandLds &L, int w, int j0, int64_t gblk
     uint32_t itemsDone = 0;
     TV(int, mnEop); // smallest predecessor position of a live candidate of the tile (BatchView::tileMinEop)
     FOR_WLANES(t, w) { TX(mnEop) = 0x7fffffff; }
+#ifdef AUGX_EMU
+    g_emuCand[EC_TILES]++; g_emuCand[EC_TILES_GT_WAVE] += totalPairs > WAVE; g_emuCand[EC_TILES_GT_DCAP] += totalPairs > DCAP;
+#endif
     for (int r0 = 0; r0 < totalPairs; r0 += WAVE) {
         if (totalPairs > WAVE) expand(r0); // (a single round: pairJ / pairS still hold it)
         const int nPr = totalPairs - r0 < WAVE ? totalPairs - r0 : WAVE;
@@ -1161,6 +1189,10 @@ AUGX_KFN void candTile(const CandCtx &X, CandLds &L, int w, int j0, int64_t gblk
         }
         waveInclScan(inc, w); waveInclScan(incA, w); waveInclScan(incE, w);
         const int nA = waveRead(incA, w, WAVE - 1), nE = waveRead(incE, w, WAVE - 1);
+#ifdef AUGX_EMU
+        g_emuCand[EC_ROUNDS_A_GT_WAVE] += nA > WAVE; g_emuCand[EC_ROUNDS_E_GT_WAVE] += nE > WAVE;
+        g_emuCand[EC_ROUNDS_A0] += nA == 0; g_emuCand[EC_ROUNDS_E0] += nE == 0;
+#endif
         FOR_WLANES(t, w) {
             const int l = t & 63;
             L.scan[w][0][l] = TX(inc) - TX(tot); L.scan[w][1][l] = TX(incA) - TX(totA); L.scan[w][2][l] = TX(incE) - TX(totE);
@@ -1173,6 +1205,11 @@ AUGX_KFN void candTile(const CandCtx &X, CandLds &L, int w, int j0, int64_t gblk
                 const int l = t & 63, f = L.scan[w][c][l], e = f + cnt[TI];
                 if (cnt[TI] > 0 && f < base + WAVE && e > base) L.head[w][(f > base ? f : base) - base] = (int8_t)l;
             }
+#ifdef AUGX_EMU
+            bool cont = false;
+            FOR_WLANES(t, w) { const int f = L.scan[w][c][t & 63]; cont |= cnt[TI] > 0 && f < base && f + cnt[TI] > base; }
+            g_emuCand[c == 1 ? EC_CHUNKS_A_CONT : EC_CHUNKS_E_CONT] += cont;
+#endif
             WAVE_SYNC();
             FOR_WLANES(t, w) { const int l = t & 63; q[TI] = L.head[w][l]; L.head[w][l] = -1; } // (cleared for the next chunk)
             waveInclMax(q, w);
@@ -1242,9 +1279,19 @@ AUGX_KFN void candTile(const CandCtx &X, CandLds &L, int w, int j0, int64_t gblk
                 FOR_WLANES(t, w) { if (TX(slow)) L.slowQ[w][nS + TX(sinc) - 1] = (uint32_t)(base + (t & 63)); }
                 nS += nNew;
                 WAVE_SYNC();
-                if (nS >= WAVE) flushSlow(WAVE);
+                // (a full queue is evaluated a wavefront at a time; a test build's lower threshold flushes SLOWQ_AT entries of a shorter
+                //  one.  Either way fewer than WAVE entries stay, so that the next chunk's fit)
+                const int cntFull = nS >= WAVE ? WAVE : SLOWQ_AT;
+#ifdef AUGX_EMU
+                if (nS > g_emuCand[EC_MAX_NS]) g_emuCand[EC_MAX_NS] = nS;
+                if (nS >= SLOWQ_AT) { g_emuCand[EC_FULL_FLUSH]++; g_emuCand[EC_FULL_FLUSH_MOVE] += nS > cntFull; }
+#endif
+                if (nS >= SLOWQ_AT) flushSlow(cntFull);
             }
         }
+#ifdef AUGX_EMU
+        g_emuCand[EC_TAIL_FLUSH] += nS > 0;
+#endif
         if (nS > 0) flushSlow(nS);
         WAVE_SYNC();
         itemsDone += (uint32_t)(nA + nE);

@@ -387,6 +387,14 @@ long long emu_jumps() { return g_emuJumps; }
 long long emu_quiet_checks() { return g_emuQuietChecks; }
 long long emu_jump_tiles() { return g_emuJumpTiles; }   // (tests: runs of N were jumped over)
 long long emu_quiet_tiles() { return g_emuQuietTiles; } // (tests: the chain-only path of trellisPiece was taken)
+// branches of candTile's pass 2 taken since the last reset (kernels.h: EmuCand, EC_N entries; EC_MAX_NS is a maximum)
+int emu_cand_coverage(long long *out) { for (int i = 0; i < EC_N; i++) out[i] = g_emuCand[i]; return EC_N; }
+void emu_cand_coverage_reset() { for (int i = 0; i < EC_N; i++) g_emuCand[i] = 0; }
+int emu_slowq_at() { return SLOWQ_AT; }
+// block size of the candidate / trellis kernels that a decode of this model takes (layout.h; AUGX_BLK applies), -1: unsupported
+int emu_block_size(const augx_tables *t) {
+    try { return chooseBlockSize(*t); } catch (std::exception &) { return -1; }
+}
 int emu_near_ties(int p) { return p >= 0 && p < (int)g_nearTies.size() ? g_nearTies[p] : -1; }
 // values of the TSS window at base 0 of the pieces of the NEXT emu_decode, [n][2] forward / reverse, NaN: the piece's own (n = 0: none)
 void emu_set_tss0(const double *v, int n) { g_tss0.assign(v, v + (v ? 2 * (size_t)n : 0)); }

@@ -450,6 +450,88 @@ def emu_state_type(tables_ptr, s):
     return _emu.emu_state_type(tables_ptr, s)
 
 
+# branches of the candidate kernel's evaluation pass (kernels.h: candTile, EmuCand), in the order of the emulator's counters
+CAND_COVERAGE = ("tiles", "tiles_gt_wave", "tiles_gt_dcap", "rounds_a_gt_wave", "rounds_e_gt_wave", "rounds_a0", "rounds_e0",
+                 "chunks_a_cont", "chunks_e_cont", "full_flush", "full_flush_move", "tail_flush", "max_ns")
+
+
+def _emu_of(lib):
+    global _emu
+    if lib is not None:
+        return ctypes.CDLL(lib)
+    if _emu is None:
+        _emu = ctypes.CDLL(EMU_LIB)
+    return _emu
+
+
+def _repeat(motif, n):
+    return (motif * (n // len(motif) + 1))[:n]
+
+
+def _gc_dna(n, gc, seed):
+    rng = random.Random(seed)
+    return "".join(rng.choice("GC") if rng.random() < gc else rng.choice("AT") for _ in range(n))
+
+
+def cand_edge_cases():
+    """[(name, sequence)] made for the evaluation pass of the candidate kernel (kernels.h: candTile, pass 2); tests/test_emu_cand.py
+    checks that they reach every branch of it.
+    - motif repeats that put reverse-strand exon ends next to dense splice sites: tiles of more than DCAP (base, state) pairs,
+      rounds with several chunks of either class, pairs whose candidates run on from one chunk into the next;
+    - pieces of 64-600 bases of short repeats: every exon pair of such a piece also has a candidate that starts at base 0 and needs
+      the general formula, so that a round queues more than a wavefront of them (the slow queue is flushed full, the rest moved);
+    - a record whose GC content steps from a low class to a high one: some piece of the batch has two classes (MULTI)"""
+    rnd = lambda n, seed: random_dna(n, 9000 + seed)
+    recs = [
+        ("accTac_rep", rnd(300, 1) + _repeat("ACCTAC", 4800) + rnd(300, 2)),
+        ("ttacta_rep", rnd(200, 3) + _repeat("TTACTACTA", 3600) + rnd(400, 4)),
+        ("gtagctac_rep", rnd(500, 5) + _repeat("GTAGCTAC", 3200) + rnd(100, 6)),
+    ]
+    # short pieces: queue fills of 64 and more (a bounded search over motifs and lengths, driven by the emulator's counters)
+    for motif, n in (("CATA", 600), ("CATA", 160), ("ATAC", 160), ("ATGGT", 600), ("ATGAGT", 100), ("CAGT", 160), ("ACTGAC", 128),
+                     ("ACCTAC", 200), ("TTACTACTA", 64), ("GTAGCTAC", 96)):
+        recs.append(("%s_%d" % (motif.lower(), n), _repeat(motif, n)))
+    recs += [("rand_%d" % n, rnd(n, n)) for n in (64, 65, 127, 160)]
+    recs.append(("twoclass", _gc_dna(9000, 0.30, 9101) + _gc_dna(7000, 0.66, 9102)))
+    return recs
+
+
+def cand_edge_long(n=260000):
+    """one record of n bases of random DNA with blocks of the motif repeats of cand_edge_cases().  At AUGX_SEG_LEN=100000 it is cut into
+    three segments (at 86 656 and 173 312 for the default n), and two of the blocks lie across the cuts: the trellis fix-ups there size
+    their check window from the candidate kernel's tile minima (BatchView::tileMinEop)"""
+    s = random_dna(n, 9200)
+    for at, motif in ((83000, "ACCTAC"), (130000, "CATA"), (170000, "TTACTACTA")):
+        s = s[:at] + _repeat(motif, 6000) + s[at + 6000:]
+    return s
+
+
+def emu_cand_coverage(lib=None, reset=False):
+    """{counter: value} of the branches candTile's pass 2 took in the emulator `lib` since its last reset (max_ns: the largest
+    fill of the slow queue); reset=True clears them afterwards"""
+    E = _emu_of(lib)
+    out = (ctypes.c_longlong * 64)()
+    n = E.emu_cand_coverage(out)
+    assert n == len(CAND_COVERAGE), n
+    if reset:
+        E.emu_cand_coverage_reset()
+    return dict(zip(CAND_COVERAGE, out[:n]))
+
+
+def emu_cand_coverage_reset(lib=None):
+    _emu_of(lib).emu_cand_coverage_reset()
+
+
+def emu_slowq_at(lib=None):
+    """the slow-queue threshold the emulator `lib` was built with (kernels.h: SLOWQ_AT)"""
+    return _emu_of(lib).emu_slowq_at()
+
+
+def emu_block_size(tables_ptr, lib=None):
+    """block size of the candidate / trellis kernels for this model (layout.h: chooseBlockSize, AUGX_BLK applies)"""
+    return _emu_of(lib).emu_block_size(tables_ptr)
+
+
 def format_gff_sampled(model, recs, paths, samples):
     """GFF text of the product's gene-structure stage with posterior probabilities (augx_format_gff_sampled): paths[k] the Viterbi
     path [(begin, end, state, type)], samples[k] the sampled paths [(begin, end, type)] of record k"""
