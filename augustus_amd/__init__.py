@@ -15,6 +15,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AUGX_LIB") or os.path.join(_HERE, "libaugx.so")  # (AUGX_LIB: a developer build of the same library)
 
+AUGX_E_ARG = -1
 AUGX_E_NODEVICE = -3
 AUGX_E_HIP = -4
 AUGX_E_UNSUPPORTED = -5
@@ -76,6 +77,8 @@ def lib():
         L.augx_batch_sync.argtypes = [ctypes.c_void_p]
         L.augx_batch_paths.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         L.augx_batch_cells.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+        L.augx_batch_prep.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
+                                      ctypes.POINTER(ctypes.c_int64)]
         L.augx_batch_kernel_ms.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_float),
                                            ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
         L.augx_batch_forward.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
@@ -141,6 +144,42 @@ class Model:
             pass
 
 
+# arrays of the preparation stage that ``augx_batch_prep`` hands out (include/augx.h: AUGX_PREP_*):
+# name -> (which, dtype, fields, layout).  "slots": every slot of the piece (its before-first slot, its bases, its pad slots), stored
+# in chunks of 1024 slots, field-major inside a chunk; "bases": one record per base (gcRaw: per GC window); "piece": per-piece scalars
+PREP_CHUNK = 1024
+PREP_ARRAYS = {
+    "code": (0, "u1", 1, "slots"), "cnt": (1, "u4", 11, "slots"), "nsm": (2, "u4", 6, "slots"), "gcRaw": (3, "u1", 1, "bases"),
+    "gcPlane": (4, "u1", 1, "bases"), "fx": (5, "u8", 20, "slots"), "sig": (6, "f8", 10, "bases"), "gate": (7, "u8", 1, "bases"),
+    "plsR": (8, "f8", 3, "bases"), "ufx": (9, "u8", 6, "slots"), "ucnt": (10, "u4", 4, "slots"), "cls": (11, "i4", 1, "piece"),
+    "nPlanes": (12, "i4", 1, "piece"), "planeCls": (13, "i4", 16, "piece"), "listCnt": (14, "i4", 1, "piece"),
+}
+
+
+def prep_fetch(call, which, plane=0):
+    """one array of the preparation stage through ``call(which, plane, out, cap_bytes, n_bytes) -> rc`` (augx_batch_prep, or the test
+    emulator's export of the same shape): [slots, fields] / [bases, fields], one-dimensional for a single field, a scalar array for
+    cls / nPlanes / listCnt"""
+    import numpy as np
+    idx, dt, nf, layout = PREP_ARRAYS[which]
+    nb = ctypes.c_int64(0)
+    rc = call(idx, plane, None, 0, ctypes.byref(nb))
+    if rc != AUGX_E_ARG or nb.value <= 0:  # (a buffer that is too small is refused with the size wanted; anything else is the refusal itself)
+        raise AugxError(rc, "no array %r, plane %d" % (which, plane))
+    raw = np.empty(nb.value, dtype=np.uint8)
+    rc = call(idx, plane, raw.ctypes.data_as(ctypes.c_void_p), nb.value, ctypes.byref(nb))
+    if rc != 0:
+        raise AugxError(rc, "array %r, plane %d" % (which, plane))
+    a = raw.view(np.dtype(dt))
+    if layout == "slots":
+        a = a.reshape(-1, nf, PREP_CHUNK).transpose(0, 2, 1).reshape(-1, nf)
+    elif layout == "bases":
+        a = a.reshape(-1, nf)
+    elif nf == 1:
+        return a.reshape(())
+    return np.ascontiguousarray(a.reshape(-1) if nf == 1 else a)
+
+
 class DecodedPiece:
     __slots__ = ("status", "ln_viterbi", "states")
 
@@ -164,7 +203,7 @@ class Batch:
             P[i].seq, P[i].len, P[i].init_kind, P[i].term_kind = s, len(s), iks[i], tks[i]
         self._h = ctypes.c_void_p()
         _check(L.augx_batch_create(decoder._h, P, self.n, ctypes.byref(self._h)))
-        decoder._batches.add(self)   # (a decoder closes its live batches before it goes: they hold a pointer to it)
+        decoder._batches.add(self._h.value)   # (a decoder destroys its live batches before it goes: they hold a pointer to it)
 
     def decode(self, sync=True):
         _check(lib().augx_batch_decode(self.decoder._h, self._h))
@@ -194,6 +233,12 @@ class Batch:
         V = np.empty((self.lens[piece], S), dtype=np.float64)
         _check(lib().augx_batch_cells(self.decoder._h, self._h, piece, V.ctypes.data_as(ctypes.c_void_p)))
         return V
+
+    def prep(self, piece, which, plane=0):
+        """test hook (``augx_batch_prep``): array ``which`` (a name of PREP_ARRAYS) of one piece as the preparation stage of the last
+        decode left it, plane ``plane`` of the arrays that have one per GC class of the piece (fx, plsR)"""
+        L = lib()
+        return prep_fetch(lambda w, pl, out, cap, nb: L.augx_batch_prep(self.decoder._h, self._h, piece, w, pl, out, cap, nb), which, plane)
 
     def forward(self):
         """run the forward algorithm on the decoded batch (``augx_batch_forward``)"""
@@ -225,7 +270,9 @@ class Batch:
 
     def close(self):
         if self._h:
-            lib().augx_batch_destroy(self._h)
+            if self._h.value in self.decoder._batches:  # (else the decoder has gone and has taken this batch with it)
+                self.decoder._batches.discard(self._h.value)
+                lib().augx_batch_destroy(self._h)
             self._h = ctypes.c_void_p()
 
     def __del__(self):
@@ -369,9 +416,11 @@ class Decoder:
     """Device context (``augx_decoder_create``).  Raises AugxError(AUGX_E_NODEVICE) without a HIP device."""
 
     def __init__(self, model, device=0):
-        import weakref
         self.model = model
-        self._batches = weakref.WeakSet()
+        # handles of the live batches.  (Not weak references to the Batch objects: when a decoder and its batches become garbage together
+        # -- held by the traceback of a failed test, say -- the collector clears weak references BEFORE it runs any __del__, the decoder
+        # found no batch to close, went, and the batches' own __del__ then reached through their pointer to it)
+        self._batches = set()
         self._h = ctypes.c_void_p()
         _check(lib().augx_decoder_create(model._h, device, ctypes.byref(self._h)))
 
@@ -405,8 +454,9 @@ class Decoder:
 
     def close(self):
         if self._h:
-            for b in list(self._batches):
-                b.close()
+            for h in list(self._batches):
+                lib().augx_batch_destroy(ctypes.c_void_p(h))
+            self._batches.clear()
             lib().augx_decoder_destroy(self._h)
             self._h = ctypes.c_void_p()
 

@@ -116,8 +116,7 @@ __global__ void __launch_bounds__(64) kClassFinal(BatchView B, const int32_t *bl
 // smoothed GC-content stairs of the pieces whose windows disagree, on the device (the same algorithm as layout.h: stairsPlanes,
 // reference ContentStairs::computeStairs, src/motif.cc:543-616): runs of equal window class, a run shorter than 1000 bases
 // between two runs of one class is dissolved, classes are numbered by first appearance (planes), every base gets its plane.
-// One workgroup per piece; a piece with more runs than STAIR_RUNS is left to the host (info[1] is set).
-constexpr int STAIR_RUNS = 4096;
+// One workgroup per piece; a piece with more runs than STAIR_RUNS (layout.h) is left to the host (info[1] is set).
 __global__ void __launch_bounds__(256) kStairs(const DevTables *__restrict__ T, BatchView B, int32_t *info /* [0] max planes, [1] pieces left to the host */) {
     const int p = blockIdx.x, t = threadIdx.x;
     if (B.cls[p] >= 0) return; // all windows agree: one class, plane 0 (gcPlane is zero)
@@ -203,7 +202,7 @@ __global__ void __launch_bounds__(256) kSiteConsts(const DevTables *__restrict__
 // 296 B per base).  The bases the terms look at are staged in LDS (SlotCodes).  Integer sums and maxima are exact: any scan
 // shape gives the same bits as the sequential loop of the emulator.  (SCAN_T = 256: several workgroups per compute unit hide
 // each other's barriers; with one workgroup of 1024 threads per chunk the scans ran 40 % longer.)
-constexpr int SCAN_T = 256, SCAN_W = SCAN_T / 64;
+constexpr int SCAN_W = SCAN_T / 64; // (SCAN_T: layout.h)
 static_assert(CHUNK % SCAN_T == 0, "scan blocks do not straddle pieces");
 template <int NF> struct ScanLds { uint64_t w[NF][SCAN_W]; };
 // inclusive scans over the 64 lanes of a wavefront: kernels.h waveScanIncl, the DPP form of the VALU moves (no trip through the LDS
@@ -1327,6 +1326,50 @@ int augx_batch_cells(augx_decoder *d, augx_batch *b, int piece, double *out) {
                 for (int s2 = 0; s2 < S; s2++) out[(size_t)q * S + s2] += brkOff[r];
         }
     }
+    return AUGX_OK;
+}
+
+int augx_batch_prep(augx_decoder *d, augx_batch *b, int piece, int which, int plane, void *out, int64_t cap_bytes, int64_t *n_bytes) {
+    if (!d || !b || !n_bytes || piece < 0 || piece >= b->V.nPieces || which < 0 || which >= AUGX_PREP_N) { setLastError("augx_batch_prep: bad argument"); return AUGX_E_ARG; }
+    *n_bytes = 0;
+    if (!b->decoded) { setLastError("augx_batch_prep: the batch has not been decoded"); return AUGX_E_ARG; }
+    HIP_TRY(hipSetDevice(d->device));
+    HIP_TRY(hipStreamSynchronize(d->stream));
+    const BatchView &V = b->V;
+    const int64_t o = b->L.off[piece], slots = b->L.off[piece + 1] - o, len = b->L.len[piece];
+    const bool planed = which == AUGX_PREP_FX || which == AUGX_PREP_PLSR;
+    int32_t nPlanes = 1;
+    if (planed) HIP_TRY(hipMemcpy(&nPlanes, V.nPlanes + piece, sizeof nPlanes, hipMemcpyDeviceToHost));
+    if (plane < 0 || plane >= nPlanes || plane >= V.nPl) { setLastError("augx_batch_prep: the piece has no such plane"); return AUGX_E_ARG; }
+    const char *src = nullptr;
+    int64_t bytes = 0;
+    // every slot of the piece of a field array (dp.h: fidx -- the chunks of a piece are contiguous); the bases of a per-base array
+    auto slotsOf = [&](const void *base, int64_t elem, int nf) { src = (const char *)base + o * nf * elem; bytes = slots * nf * elem; };
+    auto basesOf = [&](const void *base, int64_t elem, int nf, int64_t count) { src = (const char *)base + (o + 1) * nf * elem; bytes = count * nf * elem; };
+    auto perPiece = [&](const int32_t *base, int nf) { src = (const char *)(base + (int64_t)piece * nf); bytes = (int64_t)nf * sizeof(int32_t); };
+    int win = d->hostT.gc_win;
+    if (win > len || win < 1) win = (int)len;
+    switch (which) {
+    case AUGX_PREP_CODE: slotsOf(V.code, 1, 1); break;
+    case AUGX_PREP_CNT: slotsOf(V.cnt, sizeof(uint32_t), NCNT); break;
+    case AUGX_PREP_NSM: slotsOf(V.nsm, sizeof(uint32_t), 6); break;
+    case AUGX_PREP_GCRAW: basesOf(V.gcRaw, 1, 1, len - win + 1); break;
+    case AUGX_PREP_GCPLANE: basesOf(V.gcPlane, 1, 1, len); break;
+    case AUGX_PREP_FX: slotsOf(V.fx + (int64_t)plane * V.N * NFX, sizeof(uint64_t), NFX); break;
+    case AUGX_PREP_SIG: basesOf(V.sig, sizeof(double), NSIG, len); break;
+    case AUGX_PREP_GATE: basesOf(V.gate, sizeof(uint64_t), 1, len); break;
+    case AUGX_PREP_PLSR: basesOf(V.plsR + (int64_t)plane * V.N * 3, sizeof(double), 3, len); break;
+    case AUGX_PREP_UFX: if (V.ufx) slotsOf(V.ufx, sizeof(uint64_t), NUFX); break;
+    case AUGX_PREP_UCNT: if (V.ucnt) slotsOf(V.ucnt, sizeof(uint32_t), NUCNT); break;
+    case AUGX_PREP_CLS: perPiece(V.cls, 1); break;
+    case AUGX_PREP_NPLANES: perPiece(V.nPlanes, 1); break;
+    case AUGX_PREP_PLANECLS: perPiece(V.planeCls, MAXPL); break;
+    case AUGX_PREP_LISTCNT: perPiece(V.listCnt, 1); break;
+    }
+    if (!src) { setLastError("augx_batch_prep: the model has no such array"); return AUGX_E_ARG; }
+    *n_bytes = bytes;
+    if (!out || cap_bytes < bytes) { setLastError("augx_batch_prep: the buffer is too small"); return AUGX_E_ARG; }
+    HIP_TRY(hipMemcpy(out, src, (size_t)bytes, hipMemcpyDeviceToHost));
     return AUGX_OK;
 }
 

@@ -39,6 +39,11 @@ struct BatchLayout {
     }
 };
 
+// runs of equal window class the device's stairs kernel holds (decoder.hip: kStairs); a piece with more is settled on the host by stairsPlanes
+constexpr int STAIR_RUNS = 4096;
+// slots per block of the device's prefix scans (decoder.hip: one workgroup of SCAN_T threads per block, kChunkOffsets over the blocks of a piece)
+constexpr int SCAN_T = 256;
+
 // smoothed GC-content stairs of one piece from the classes of its windows (reference ContentStairs::computeStairs,
 // src/motif.cc:543-616): wc[s] = class of the window of `win` bases starting at base s, s in [0, n - win] (win already
 // clamped to n).  Base i has the class of the window centred on it, the ends that of the first / last window; a step

@@ -305,6 +305,18 @@ int augx_batch_kernel_ms(augx_decoder *d, augx_batch *b, float *prep_ms, float *
 /* test hook: copy the dense ln V[j][s] matrix (len*S doubles, -inf = absent) of piece i to host; only
  * valid on a decoder created with AUGX_DEBUG_CELLS=1 in the environment */
 int augx_batch_cells(augx_decoder *d, augx_batch *b, int piece, double *out);
+/* test hook: copy what the preparation stage of the last augx_batch_decode left for piece i of one array to the host (after
+ * augx_batch_sync; no kernel is launched, nothing the decode does changes).  `which` is one of AUGX_PREP_*:
+ *   CODE, CNT (NCNT fields), NSM (6), FX of one plane (NFX), UFX (NUFX), UCNT (NUCNT): every slot of the piece, off[i] .. off[i + 1],
+ *     in the device layout (chunks of 1024 slots, field-major inside a chunk);
+ *   GCPLANE, SIG (10 doubles per base), GATE, PLSR of one plane (3 doubles per base): the len bases of the piece;
+ *   GCRAW: the class of every GC window of the piece, len - win + 1 window starts (win = GCwinsize, at most len);
+ *   CLS, NPLANES, PLANECLS (AUGX_MAX_CLASSES entries), LISTCNT: the per-piece scalars, int32.
+ * *n_bytes receives the size of the array.  AUGX_E_ARG: the batch has not been decoded, the piece has no such plane (plane must be 0
+ * for the arrays without planes), the model has no such array (UFX, UCNT: dense kernels only), or cap_bytes < *n_bytes */
+enum { AUGX_PREP_CODE = 0, AUGX_PREP_CNT, AUGX_PREP_NSM, AUGX_PREP_GCRAW, AUGX_PREP_GCPLANE, AUGX_PREP_FX, AUGX_PREP_SIG, AUGX_PREP_GATE,
+       AUGX_PREP_PLSR, AUGX_PREP_UFX, AUGX_PREP_UCNT, AUGX_PREP_CLS, AUGX_PREP_NPLANES, AUGX_PREP_PLANECLS, AUGX_PREP_LISTCNT, AUGX_PREP_N };
+int augx_batch_prep(augx_decoder *d, augx_batch *b, int piece, int which, int plane, void *out, int64_t cap_bytes, int64_t *n_bytes);
 /* forward algorithm of a decoded batch (reference NAMGene::viterbiAndForward with needForwardTable, src/namgene.cc:168-365,
  * the per-state `fwdsum`s): the dense ln F matrix stays on the device for the posterior sampling; the second call copies the
  * len*S matrix of one piece (-inf = absent) and ln P(sequence) to the host (tests; the executable's --sample > 0 goes through

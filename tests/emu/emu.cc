@@ -38,6 +38,45 @@ template <bool MAX, class E> void scanFields(E *a, int nf, const BatchLayout &L)
 }
 } // namespace
 
+// ---- what the preparation stage of the last emu_decode left (emu_prep_keep(1) before it), handed out by emu_prep in the layout
+//      of augx_batch_prep (include/augx.h): the device's arrays are compared with these one by one (tests/test_gpu_prep.py)
+namespace {
+struct PrepSnap {
+    bool have = false, dense = false;
+    BatchLayout L;
+    int gcWin = 0, nPl = 1;
+    std::vector<uint8_t> code, gcRaw, gcPlane;
+    std::vector<uint32_t> cnt, nsm, ucnt;
+    std::vector<uint64_t> fx, gate, ufx;
+    std::vector<double> sig, plsR;
+    std::vector<int32_t> cls, nPlanes, planeCls, listCnt, runs;
+};
+bool g_keepPrep = false;
+PrepSnap g_prep;
+void snapPrep(const augx_tables *t, const BatchLayout &L, const BatchView &B, bool dense) {
+    PrepSnap &P = g_prep;
+    P = PrepSnap();
+    if (!g_keepPrep) return;
+    const int64_t N = L.N;
+    const int n = L.nPieces;
+    P.have = true; P.dense = dense; P.L = L; P.gcWin = t->gc_win; P.nPl = B.nPl;
+    P.code.assign(B.code, B.code + N); P.gcRaw.assign(B.gcRaw, B.gcRaw + N); P.gcPlane.assign(B.gcPlane, B.gcPlane + N);
+    P.cnt.assign(B.cnt, B.cnt + N * NCNT); P.nsm.assign(B.nsm, B.nsm + N * 6);
+    P.fx.assign(B.fx, B.fx + (int64_t)B.nPl * N * NFX); P.plsR.assign(B.plsR, B.plsR + (int64_t)B.nPl * N * 3);
+    P.sig.assign(B.sig, B.sig + N * NSIG); P.gate.assign(B.gate, B.gate + N);
+    if (dense) { P.ufx.assign(B.ufx, B.ufx + N * NUFX); P.ucnt.assign(B.ucnt, B.ucnt + N * NUCNT); }
+    P.cls.assign(B.cls, B.cls + n); P.nPlanes.assign(B.nPlanes, B.nPlanes + n); P.planeCls.assign(B.planeCls, B.planeCls + (int64_t)n * MAXPL);
+    P.listCnt.assign(B.listCnt, B.listCnt + n);
+    P.runs.assign((size_t)n, 1);
+    for (int p = 0; p < n; p++) { // runs of equal window class as kStairs counts them: 1 + the window starts 1 .. len - win whose class differs from the one before
+        int win = t->gc_win;
+        if (win > L.len[p] || win < 1) win = L.len[p];
+        const uint8_t *wc = B.gcRaw + L.off[p] + 1;
+        for (int s0 = 1; s0 <= L.len[p] - win; s0++) P.runs[(size_t)p] += wc[s0] != wc[s0 - 1];
+    }
+}
+} // namespace
+
 
 
 // posterior sampling in the emulator: emu_set_sampling(n, seed) before emu_decode(..., fwd_out != NULL); the generator lives on
@@ -154,6 +193,7 @@ static int emu_decode_dense(const augx_tables *t, const augx_piece *pieces, int 
     for (int pl = 0; pl < B.nPl; pl++)
         for (int64_t g = 0; g < B.N; g++) k1SiteConsts(T, B, g, pl);
     for (int64_t g = 0; g < B.N; g++) k1UtrSignals(T, B, g);
+    snapPrep(t, L, B, true);
     // candidate records of the coding exons and short introns, in their dense form
     B.blk = blk;
     B.nBlk = B.N / blk;
@@ -395,6 +435,52 @@ int emu_slowq_at() { return SLOWQ_AT; }
 int emu_block_size(const augx_tables *t) {
     try { return chooseBlockSize(*t); } catch (std::exception &) { return -1; }
 }
+// the preparation arrays of the last emu_decode are kept for emu_prep (off by default: they are as large as the batch's own)
+void emu_prep_keep(int on) { g_keepPrep = on != 0; if (!on) g_prep = PrepSnap(); }
+int emu_gc_win(const augx_tables *t) { return t->gc_win; }          // (GCwinsize as the model loaded it)
+int emu_n_classes(const augx_tables *t) { return t->n_classes; }    // (GC-content classes of the model)
+int emu_stair_runs() { return STAIR_RUNS; }   // (layout.h: the runs of window classes the device's stairs kernel holds)
+int emu_scan_block() { return SCAN_T; }       // (layout.h: slots per block of the device's prefix scans)
+int emu_prep_runs(int p) { return g_prep.have && p >= 0 && p < g_prep.L.nPieces ? g_prep.runs[(size_t)p] : -1; }
+long long emu_prep_off(int p) { return g_prep.have && p >= 0 && p <= g_prep.L.nPieces ? (long long)g_prep.L.off[(size_t)p] : -1; }
+// as augx_batch_prep (include/augx.h): array `which` (AUGX_PREP_*) of piece p, same layout, same refusals
+int emu_prep(int p, int which, int plane, void *out, int64_t cap_bytes, int64_t *n_bytes) {
+    const PrepSnap &P = g_prep;
+    if (!P.have || !n_bytes || p < 0 || p >= P.L.nPieces || which < 0 || which >= AUGX_PREP_N) return AUGX_E_ARG;
+    *n_bytes = 0;
+    const bool planed = which == AUGX_PREP_FX || which == AUGX_PREP_PLSR;
+    if (plane < 0 || plane >= (planed ? P.nPlanes[(size_t)p] : 1)) return AUGX_E_ARG;
+    const int64_t o = P.L.off[(size_t)p], slots = P.L.off[(size_t)p + 1] - o, len = P.L.len[(size_t)p], N = P.L.N;
+    int win = P.gcWin;
+    if (win > len || win < 1) win = (int)len;
+    const char *src = nullptr;
+    int64_t bytes = 0;
+    auto slotsOf = [&](const void *base, int64_t elem, int nf) { src = (const char *)base + o * nf * elem; bytes = slots * nf * elem; };
+    auto basesOf = [&](const void *base, int64_t elem, int nf, int64_t count) { src = (const char *)base + (o + 1) * nf * elem; bytes = count * nf * elem; };
+    auto perPiece = [&](const int32_t *base, int nf) { src = (const char *)(base + (int64_t)p * nf); bytes = (int64_t)nf * sizeof(int32_t); };
+    switch (which) {
+    case AUGX_PREP_CODE: slotsOf(P.code.data(), 1, 1); break;
+    case AUGX_PREP_CNT: slotsOf(P.cnt.data(), 4, NCNT); break;
+    case AUGX_PREP_NSM: slotsOf(P.nsm.data(), 4, 6); break;
+    case AUGX_PREP_GCRAW: basesOf(P.gcRaw.data(), 1, 1, len - win + 1); break;
+    case AUGX_PREP_GCPLANE: basesOf(P.gcPlane.data(), 1, 1, len); break;
+    case AUGX_PREP_FX: slotsOf(P.fx.data() + (int64_t)plane * N * NFX, 8, NFX); break;
+    case AUGX_PREP_SIG: basesOf(P.sig.data(), 8, NSIG, len); break;
+    case AUGX_PREP_GATE: basesOf(P.gate.data(), 8, 1, len); break;
+    case AUGX_PREP_PLSR: basesOf(P.plsR.data() + (int64_t)plane * N * 3, 8, 3, len); break;
+    case AUGX_PREP_UFX: if (P.dense) slotsOf(P.ufx.data(), 8, NUFX); break;
+    case AUGX_PREP_UCNT: if (P.dense) slotsOf(P.ucnt.data(), 4, NUCNT); break;
+    case AUGX_PREP_CLS: perPiece(P.cls.data(), 1); break;
+    case AUGX_PREP_NPLANES: perPiece(P.nPlanes.data(), 1); break;
+    case AUGX_PREP_PLANECLS: perPiece(P.planeCls.data(), MAXPL); break;
+    case AUGX_PREP_LISTCNT: perPiece(P.listCnt.data(), 1); break;
+    }
+    if (!src) return AUGX_E_ARG;
+    *n_bytes = bytes;
+    if (!out || cap_bytes < bytes) return AUGX_E_ARG;
+    memcpy(out, src, (size_t)bytes);
+    return 0;
+}
 int emu_near_ties(int p) { return p >= 0 && p < (int)g_nearTies.size() ? g_nearTies[p] : -1; }
 // values of the TSS window at base 0 of the pieces of the NEXT emu_decode, [n][2] forward / reverse, NaN: the piece's own (n = 0: none)
 void emu_set_tss0(const double *v, int n) { g_tss0.assign(v, v + (v ? 2 * (size_t)n : 0)); }
@@ -553,6 +639,7 @@ int emu_decode(const augx_tables *t, const augx_piece *pieces, int n, double *ln
         for (int64_t t2 = 0; t2 < B.listCap; t2++) k1SiteSignals(T, B, t2, sel);
     for (int pl = 0; pl < B.nPl; pl++)
         for (int64_t g = 0; g < B.N; g++) k1SiteConsts(T, B, g, pl);
+    snapPrep(t, L, B, false);
     // ---- K2a: candidates, tile by tile (first with buffers that are too small, to exercise the re-run path)
     B.blk = blk;
     B.nBlk = B.N / blk;

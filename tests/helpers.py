@@ -387,7 +387,7 @@ class _Piece(ctypes.Structure):
 _emu = None
 
 
-def emu_decode(tables_ptr, seqs, S, cells=False, init_kind=0, term_kind=0, lib=None, forward=False, samples=0, seed=1, tss0=None):
+def emu_decode(tables_ptr, seqs, S, cells=False, init_kind=0, term_kind=0, lib=None, forward=False, samples=0, seed=1, tss0=None, prep=False):
     """Run the device kernel bodies on the CPU (tests/emu/emu.cc).  Returns [(status, lnv, path, V, cls)]
     (forward=True: [(status, lnv, path, V, cls, F, lnP)] with the ln forward matrix F and ln P(sequence);
     samples=n: [(status, lnv, path, V, cls, F, lnP, [n sampled paths of (begin, end, type)])], drawn from one rand() stream over seqs)."""
@@ -415,6 +415,7 @@ def emu_decode(tables_ptr, seqs, S, cells=False, init_kind=0, term_kind=0, lib=N
     FW = np.zeros(tot * S) if forward else None
     lnF = np.zeros(n)
     E = _emu_lib if lib is not None else _emu
+    E.emu_prep_keep(1 if prep else 0)  # (emu_prep below reads what this decode's preparation stage left)
     E.emu_set_sampling(samples, seed)
     if tss0 is not None:  # [(forward, reverse) or None per piece]: the value of the TSS window at base 0 an earlier sequence left (BatchView::tss0)
         tv = np.array([[float('nan')] * 2 if t is None else list(t) for t in tss0], dtype=np.float64)
@@ -599,3 +600,201 @@ def gff_body(stdout_text):
     lines = stdout_text.splitlines()
     i0 = [k for k, l in enumerate(lines) if l.startswith("# ----- prediction")][0]
     return [l for l in lines[i0:] if not l.startswith("# command line")][:-1]
+
+
+# ---------------------------------------------------------------------------------------------------
+# the preparation stage of a decode, array by array (tests/test_emu_prep.py, tests/test_gpu_prep.py)
+# ---------------------------------------------------------------------------------------------------
+def emu_prep(piece, which, plane=0, lib=None):
+    """array `which` (a name of augustus_amd.PREP_ARRAYS) of one piece as the preparation stage of the last emu_decode(..., prep=True)
+    left it: the emulator's counterpart of Batch.prep, same layout, same refusals"""
+    import augustus_amd as ax
+    E = _emu_of(lib)
+    E.emu_prep.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]
+    return ax.prep_fetch(lambda w, pl, out, cap, nb: E.emu_prep(piece, w, pl, out, cap, nb), which, plane)
+
+
+def emu_prep_runs(piece, lib=None):
+    """runs of equal GC-window class of one piece of the last emu_decode(..., prep=True), as the device's stairs kernel counts them"""
+    return _emu_of(lib).emu_prep_runs(piece)
+
+
+def emu_prep_off(piece, lib=None):
+    """first slot of piece `piece` in the batch of the last emu_decode(..., prep=True) (piece = number of pieces: the batch's slots)"""
+    E = _emu_of(lib)
+    E.emu_prep_off.restype = ctypes.c_longlong
+    return E.emu_prep_off(piece)
+
+
+def stair_runs(lib=None):
+    """layout.h: STAIR_RUNS, the runs of window classes the device's stairs kernel holds (a piece with more goes to the host)"""
+    return _emu_of(lib).emu_stair_runs()
+
+
+def scan_block(lib=None):
+    """layout.h: SCAN_T, slots per block of the device's prefix scans"""
+    return _emu_of(lib).emu_scan_block()
+
+
+def emu_gc_win(tables_ptr, lib=None):
+    return _emu_of(lib).emu_gc_win(tables_ptr)
+
+
+def emu_n_classes(tables_ptr, lib=None):
+    return _emu_of(lib).emu_n_classes(tables_ptr)
+
+
+def _ag_window(win, k):
+    """a window of A with k G spread evenly, a G first"""
+    return ["G" if (i * k) // win != ((i - 1) * k) // win else "A" for i in range(win)]
+
+
+def _toggle_seq(win, k, n, want):
+    """n bases whose GC windows hold k or k - 1 G: the first window is _ag_window(win, k); every further base copies the base one window
+    back, so that the window that begins at s holds what the one before it held -- except at the window starts in `want` (ascending,
+    each put off until the base that leaves is of the kind that can be turned), where the base that enters is the other kind than the
+    base that leaves: a G leaves and an A enters (k -> k - 1), next time an A leaves and a G enters (k - 1 -> k), and so on.
+    Returns (sequence, the window starts where the count really changed)."""
+    seq = _ag_window(win, k)
+    full, done, j = True, [], 0
+    for i in range(win, n):
+        s, b = i - win + 1, seq[i - win]
+        if j < len(want) and s >= want[j] and b == ("G" if full else "A"):
+            b = "A" if full else "G"
+            full = not full
+            done.append(s)
+            j += 1
+        seq.append(b)
+    return "".join(seq), done
+
+
+def _class_boundary(m):
+    """(k, class of a window of A with k G, class with k - 1 G) at a boundary between two GC classes of model m, by bisection on the
+    emulator's window classes (it depends on the model files)"""
+    win = emu_gc_win(m.tables_ptr)
+
+    def cls(k):
+        emu_decode(m.tables_ptr, ["".join(_ag_window(win, k))], m.n_states, prep=True)
+        return int(emu_prep(0, "gcRaw")[0])
+    lo, hi = 0, win // 2
+    c0 = cls(lo)
+    assert cls(hi) != c0, "a window of A and one that is half G have one GC class"
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        if cls(mid) == c0:
+            lo = mid
+        else:
+            hi = mid
+    return hi, cls(hi), c0
+
+
+_prep_cases = {}
+
+# the records of prep_edge_cases that every configuration decodes (the others: the models with two or more GC classes whose window
+# is GCwinsize, i.e. the human ones)
+PREP_COMMON = ("planes_unordered", "n_window", "blocks_64", "sites_after_blocks_64", "blocks_68", "blocks_128", "blocks_132")
+TINY_LENS = (1, 7, 255, 1014, 1015, 1016, 2039)
+
+
+def prep_edge_cases(m, key):
+    """[(name, sequence)] made for the preparation stage of a decode (decoder.hip: the kernels before kCand), in batch order;
+    tests/test_emu_prep.py asserts from the emulator's arrays that each record meets the condition it is named for.  `key` names the
+    configuration of model m (the records are built once per configuration).
+    - runs_over / runs_at / runs_at_plus1: more runs of GC-window classes than the device's stairs kernel holds (layout.h: STAIR_RUNS;
+      the host settles the piece), exactly as many, one more.  The window count of G moves across a class boundary and back every few
+      bases (_toggle_seq); the two others are the same sequence cut where the run count reaches the limit;
+    - one_plane_after_smoothing, short_run_first, step_999 / step_1000: a run of the other class of 999 positions or fewer between two
+      runs of one class is dissolved, one of 1000 stays; a short run right after run 0 (one window);
+    - planes_unordered: stretches longer than the GC window whose GC content falls from 0.72 to 0.24: the classes appear high to low,
+      so the planes (numbered by first appearance) are not in class order;
+    - below_window .. window_plus_300: pieces shorter than, as long as, and a little longer than the GC window; class_in_block_1_only:
+      the second class shows in the windows of one block of 256 slots only;
+    - blocks_*: pieces of exactly 64, 68, 128 and 132 scan blocks (a piece takes len + 9 slots rounded up to a chunk of 4 blocks);
+    - tiny_*: a site-dense motif repeat cut to lengths around a chunk; sites_*: site-dense neighbours of the pieces whose pad is short
+      (1015 and 16 375 bases leave 9 pad slots) and a repeat with a period coprime to the scan block;
+    - n_window (windows without a nucleotide), softmasked (lower-case stretches: the soft-mask count)."""
+    if key in _prep_cases:
+        return _prep_cases[key]
+    win, ncls = emu_gc_win(m.tables_ptr), emu_n_classes(m.tables_ptr)
+    rnd = lambda n, seed: random_dna(n, 9300 + seed)
+    unit = "ACCTAC" + "TTACTACTA" + "GTAGCTAC" + "CATA" + "ATGGT" + "ATGAGT" + "CAGT" + "ACTGAC" + "T"  # the motifs of cand_edge_cases
+    assert len(unit) % 2 == 1  # (coprime to the scan block of 256 slots: every site kind lands on every slot of a block)
+    gcs = (0.72, 0.66, 0.62, 0.58, 0.54, 0.50, 0.46, 0.42, 0.38, 0.34, 0.30, 0.24)
+    stretch = max(12000, win + 2000)
+    common = {
+        "planes_unordered": "".join(_gc_dna(stretch, gc, 9400 + i) for i, gc in enumerate(gcs)),
+        "n_window": n_window_record()[1],
+        "blocks_64": rnd(16375, 1), "blocks_68": rnd(16376, 2), "blocks_128": rnd(32759, 3), "blocks_132": rnd(32760, 4),
+        "sites_after_blocks_64": _repeat("ACCTAC", 700),
+    }
+    recs = []
+    if key.startswith("human"):
+        k, c_full, c_less = _class_boundary(m)
+        # (an odd number of changes: the last 3500 windows keep the other class, the piece has two planes after the smoothing)
+        over, tg = _toggle_seq(win, k, win + 30000, list(range(1, 26000, 4)) + [26500])
+        assert len(tg) % 2 == 1
+        limit = stair_runs()
+        assert len(tg) > limit + 8
+        # run r begins at window start tg[r - 1]: a piece cut to win + s bases has the window starts 0 .. s
+        recs += [("runs_over", over), ("runs_at", over[:win + tg[limit - 2]]), ("runs_at_plus1", over[:win + tg[limit - 1]])]
+        recs.append(("one_plane_after_smoothing", _toggle_seq(win, k, win + 4000, [500, 560, 1200, 1500, 2400, 2410])[0]))
+        for L in (999, 1000):  # a window start where a G leaves, and L starts later an A
+            s1 = next(s for s in range(1500, 1500 + win) if _toggle_seq(win, k, win + s + L + 1, [s, s + L])[1] == [s, s + L])
+            recs.append(("step_%d" % L, _toggle_seq(win, k, win + s1 + L + 2500, [s1, s1 + L])[0]))
+        recs.append(("short_run_first", _toggle_seq(win, k, win + 2500, [1, 300])[0]))
+        recs += [("below_window", rnd(win - 1, 5)), ("at_window", rnd(win, 6)),
+                 ("window_plus_1", _toggle_seq(win, k, win + 1, [1])[0]), ("window_plus_300", _toggle_seq(win, k, win + 300, [100, 200])[0])]
+        # the only windows of the second class lie in the piece's second block of 256 slots (kClassFinal folds the blocks of a piece,
+        # one per lane); they are the last run, which the smoothing keeps however short
+        recs.append(("class_in_block_1_only", _toggle_seq(win, k, win + 300, [260])[0]))
+        recs.append(("sites_first", _repeat("TTACTACTA", 900)))
+        for n in TINY_LENS:
+            recs.append(("tiny_%d" % n, _repeat("GTAGCTAC" + "ATGGT" + "CATA", n)))
+            if n == 1015:
+                recs.append(("sites_after_tiny_1015", _repeat("CATA", 600)))
+        sm = list(rnd(9000, 7))
+        for a, b in ((0, 40), (700, 1900), (1023, 1025), (4000, 4001), (8200, 9000)):
+            sm[a:b] = "".join(sm[a:b]).lower()
+        recs += [("sites_all_alignments", _repeat(unit, 256 * len(unit) + 100)), ("softmasked", "".join(sm))]
+    recs += [(name, common[name]) for name in PREP_COMMON]
+    _prep_cases[key] = recs
+    return recs
+
+
+def prep_one_plane_piece(m, n):
+    """n bases (more than the GC window + 3000) whose windows change class six times in short runs that the smoothing dissolves: the
+    record one_plane_after_smoothing of prep_edge_cases at another length"""
+    win = emu_gc_win(m.tables_ptr)
+    assert n >= win + 3000
+    return _toggle_seq(win, _class_boundary(m)[0], n, [500, 560, 1200, 1500, 2400, 2410])[0]
+
+
+PREP_CFGS = {**{k: GOLDEN_CFGS[k] for k in ("human", "human_utr")}, "nasonia": MORE_CFGS["nasonia"],
+             "maize": ("maize", {"UTR": "off", "sample": "0", "softmasking": "0"})}
+
+
+def prep_arrays(fetch, piece, dense):
+    """every array of the preparation stage of one piece through fetch(piece, which, plane): [(which, plane, array)], the arrays with
+    one plane per GC class of the piece once per plane, planeCls cut to the planes the piece has"""
+    npl = int(fetch(piece, "nPlanes", 0))
+    out = [("nPlanes", 0, np.asarray(npl))]
+    for which in ("cls", "planeCls", "listCnt", "code", "cnt", "nsm", "gcRaw", "gcPlane", "sig", "gate") + (("ufx", "ucnt") if dense else ()):
+        a = fetch(piece, which, 0)
+        out.append((which, 0, a[:npl] if which == "planeCls" else a))
+    for which in ("fx", "plsR"):
+        out += [(which, pl, fetch(piece, which, pl)) for pl in range(npl)]
+    return out
+
+
+def prep_first_diff(got, want):
+    """None if the two arrays are equal bit for bit (doubles through their bit patterns: -inf, signed zeros and NaN payloads count),
+    else a text that names the first position (row = slot or base) and the field that differ"""
+    if got.dtype != want.dtype or got.shape != want.shape:
+        return "dtype / shape %s %s against %s %s" % (got.dtype, got.shape, want.dtype, want.shape)
+    a, b = (x.view(np.uint64) if x.dtype == np.float64 else x for x in (np.ascontiguousarray(got), np.ascontiguousarray(want)))
+    if np.array_equal(a, b):
+        return None
+    bad = np.argwhere(np.atleast_1d(a != b))
+    first = tuple(int(x) for x in bad[0])
+    return "%d of %d values differ, first at position %d field %d: %r against %r" % (
+        len(bad), a.size, first[0], first[1] if len(first) > 1 else 0, np.atleast_1d(got)[first], np.atleast_1d(want)[first])
