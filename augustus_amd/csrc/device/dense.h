@@ -738,7 +738,7 @@ struct DenseLds {
     double ring[WAVE][SPX];          // the newest 64 columns, [j & 63][state]
     double cmax[2][8][SPX];             // variable-length cells of the block ([parity]): largest candidate ...
     unsigned long long csum[2][8][SPX]; // ... (forward) sum of exp(candidate - largest), fixed point
-    double tr[SPX][AUGX_MAX_ANC];    // ln t(ancestor ai -> s) of the piece's first class
+    double tr[SPX][AUGX_MAX_ANC];    // ln t(ancestor ai -> s) of the piece's first class (MODE 1: times the heat, as sg below)
     uint8_t anc[SPX][AUGX_MAX_ANC], nanc[SPX];
     uint8_t cellKind[SPX];           // 1: candidates from the records of kCand, 2: reverse terminal exon, 3: UTR exon, 0: none
     double sg[2][8][NSIG];           // signal records of the block ([parity]; the next block's are staged meanwhile)
@@ -794,9 +794,16 @@ AUGX_KFN void densePiece(const DevTables &T, const BatchView &B, DenseLds &L, in
     const int dssWhole = T.Ds + 2 + T.De, assLag = T.As + 2 + T.Ae + T.U, dL = T.dStateLen;
     auto clsAt = [&](int j) __attribute__((always_inline)) { return multi ? (int)gp(gPlaneCls)[gp(gPlane)[j]] : c0; };
     const double *gTrans = T.ln_trans;
-    // ln t(a -> s2), a = ancestor ai of s2, with the class of the end base
+    // --temperature (MODE 1 only; reference LLDouble::heated, src/lldouble.cc:209-264): the factor transition x emission of every summand
+    // is raised to the power heat = (8 - t) / 8, the predecessor's value is not -- in ln, heat * (ln t + ln e).  The transition terms
+    // and the signal records are scaled where they are staged into LDS (L.tr, L.sg), the te of a candidate and a transition term from
+    // HBM where they are used; the scaled terms are exact (heat is a multiple of 1/8, the terms multiples of 2^-31 far below 2^19), so
+    // their sum is the scaled sum, and heat = 1.0 changes no bit.  MODE 0 compiles to what it did without: H is the identity there.
+    const double heat = FWD ? T.heat : 1.0;
+    auto H = [&](double x) __attribute__((always_inline)) -> double { if (FWD) return heat * x; return x; };
+    // ln t(a -> s2), a = ancestor ai of s2, with the class of the end base (MODE 1: times the heat)
     auto trn = [&](int cc, int s2, int ai) __attribute__((always_inline)) -> double {
-        if (multi) return gp(gTrans)[((int64_t)cc * S + (*lp(&L.anc[s2][ai]))) * S + s2];
+        if (multi) return H(gp(gTrans)[((int64_t)cc * S + (*lp(&L.anc[s2][ai]))) * S + s2]);
         return ldsLoadD(&L.tr[s2][ai]);
     };
     UCtx UX(T, B, p);
@@ -812,7 +819,7 @@ AUGX_KFN void densePiece(const DevTables &T, const BatchView &B, DenseLds &L, in
             for (int ai = 0; ai < AUGX_MAX_ANC; ai++) {
                 const int a = (t < S && ai < T.n_anc[t]) ? T.anc[t][ai] : 0;
                 (*lp(&L.anc[t][ai])) = (uint8_t)a;
-                (*lp(&L.tr[t][ai])) = (t < S && ai < T.n_anc[t]) ? lnT(T, c0, a, t) : AUGX_NINF;
+                (*lp(&L.tr[t][ai])) = (t < S && ai < T.n_anc[t]) ? H(lnT(T, c0, a, t)) : AUGX_NINF;
             }
         }
         for (int64_t i = t; i < (int64_t)n * S; i += NT) gp(M)[i] = AUGX_NINF; // (absent cells stay -inf)
@@ -912,7 +919,7 @@ AUGX_KFN void densePiece(const DevTables &T, const BatchView &B, DenseLds &L, in
     constexpr int NTW = NT - WAVE;
     FOR_THREADS(t) { // block 0: offsets, signal records, gates
         if (t == NT - 1) { (*lp(&L.bOff[0])) = gp(gBlkOff)[gb0 * 2 + 1]; (*lp(&L.bCnt[0][0])) = gp(gBlkCnt)[gb0 * 2 + 1]; (*lp(&L.bCnt[0][1])) = gp(gBlkSplit)[gb0 * 3 + 2]; }
-        if (t >= NT - BLK * NSIG) { const int i = t - (NT - BLK * NSIG); (*lp(&L.sg[0][i / NSIG][i % NSIG])) = i / NSIG < n ? gp(gSig)[(int64_t)(i / NSIG) * NSIG + i % NSIG] : AUGX_NINF; }
+        if (t >= NT - BLK * NSIG) { const int i = t - (NT - BLK * NSIG); (*lp(&L.sg[0][i / NSIG][i % NSIG])) = i / NSIG < n ? H(gp(gSig)[(int64_t)(i / NSIG) * NSIG + i % NSIG]) : AUGX_NINF; }
         if (nUv > 0) { // the descriptors of block 0
             const uint64_t uo = gp(gUdOff)[gb0];
             const uint32_t uc = gp(gUdCnt)[gb0];
@@ -1039,7 +1046,7 @@ AUGX_KFN void densePiece(const DevTables &T, const BatchView &B, DenseLds &L, in
                 fprintf(stderr, "emu: in-block predecessor that is not a fixed-lag state: state %d kind %d j %d eop %d jb %d src %d\n", s2, T.kind[s2], jb + dj, eop, jb, (int)(I.src & 127u));
 #endif
             const double pv = denseAt<FWD>(L, M, S, eop, (int)(I.src & 127u), jb, BLK);
-            return pv + I.te;
+            return pv + H(I.te);
         };
         auto itemPass = [&](uint32_t lo2, uint32_t hi2, bool sumPass) __attribute__((always_inline)) {
             FOR_THREADS(t) {
@@ -1120,7 +1127,7 @@ AUGX_KFN void densePiece(const DevTables &T, const BatchView &B, DenseLds &L, in
                                 const double cm = sumPass ? (*lp(&L.cmax[par][dj][s2])) : 0.0;
                                 _Pragma("unroll") for (int h = 0; h < UH; h++) {
                                     if (!act[h] || !(lnLen[h] > AUGX_NINF)) continue;
-                                    const double te = sig[h] + lnLen[h];
+                                    const double te = H(sig[h] + lnLen[h]); // (the whole emission of the candidate, pre-evaluated ones included)
                                     if (!(te > AUGX_NINF)) continue;
 #ifdef AUGX_EMU
                                     if (eop[h] >= jb && only < 0 && getenv("AUGX_EMU_CHECK_LAG")) fprintf(stderr, "emu: in-block predecessor of a UTR exon: state %d j %d eop %d jb %d\n", s2, D.j, eop[h], jb);
@@ -1167,7 +1174,7 @@ AUGX_KFN void densePiece(const DevTables &T, const BatchView &B, DenseLds &L, in
             }
             if (b + 1 < nBlocks && t >= A1T - BLK * NSIG && t < A1T) {
                 const int i = t - (A1T - BLK * NSIG), dj = i / NSIG, j = jb + BLK + dj;
-                (*lp(&L.sg[par ^ 1][dj][i % NSIG])) = j < n ? gp(gSig)[(int64_t)j * NSIG + i % NSIG] : AUGX_NINF;
+                (*lp(&L.sg[par ^ 1][dj][i % NSIG])) = j < n ? H(gp(gSig)[(int64_t)j * NSIG + i % NSIG]) : AUGX_NINF;
             }
             if (nUv > 0 && b + 1 < nBlocks && t < A1T) { // the next block's descriptors
                 const uint64_t uo = gp(gUdOff)[gb + 1];

@@ -156,6 +156,8 @@ struct DevTables {
     TabPtr ln_trans, ig_emi, ig_short, in_emi, ex_emi, ex_init, ex_et, ex_pls, tis_motif, ass_motif,
         tis_bin_bounds, tis_bin_ln, ass_pat, dss_pat, len_intron, len_single, len_initial, len_internal,
         len_terminal;
+    double heat;               // augx_tables::heat: power of transition x emission in the forward summands (1.0: cold).  Last, so that
+                               // no field the Viterbi kernels read moves
 };
 
 // a batch of pieces laid out in one slot space.  Piece p owns slots [off[p], off[p+1]); slot off[p] is the

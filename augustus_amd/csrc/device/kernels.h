@@ -2759,8 +2759,8 @@ struct FwdLds {
     double ring[WAVE][SP];   // ln F of the last 64 columns, [j & 63][state]
     double cmax[8][SP];      // variable-length cells of the current block: largest candidate ...
     unsigned long long csum[8][SP]; // ... and the sum of exp(candidate - largest), fixed point (FWD_FIX)
-    double lt[SP][SP];       // ln transition a -> s of the piece's first class (a piece with one class never leaves it)
-    double sg[2][8][NSIG];   // signal records of the block ([parity of the block]; the next block's are staged meanwhile)
+    double lt[SP][SP];       // ln transition a -> s of the piece's first class (a piece with one class never leaves it), times the heat
+    double sg[2][8][NSIG];   // signal records of the block, times the heat ([parity of the block]; the next block's are staged meanwhile)
     uint64_t bOff[2];        // candidates of the block: first record ...
     uint32_t bCnt[2][2];     // ... their number, and how many of them are not RTERMINAL  ([parity of the block])
     uint8_t anc[SP][4];      // ancestor ai of a variable-length state (the candidate records name it by index)
@@ -2794,10 +2794,16 @@ AUGX_KFN void forwardPiece(const DevTables &T, const BatchView &B, FwdLds &L, in
     if (c0 < 0) { FOR_THREADS(t) { if (t == 0) B.lnFwd[p] = AUGX_NINF; } return; }
     const bool multi = B.nPlanes[p] > 1;
     const int dssWhole = T.Ds + 2 + T.De, assLag = T.As + 2 + T.Ae + T.U, dL = T.dStateLen;
+    // --temperature (reference LLDouble::heated, src/lldouble.cc:209-264): the factor transition x emission of every summand is raised to
+    // the power heat = (8 - t) / 8, the predecessor's value is not -- in ln, heat * (ln t + ln e).  The transition terms and the signal
+    // records are scaled once, where they are staged into LDS (L.lt, L.sg: nothing else reads them), the candidates' te and a
+    // transition term fetched from HBM where they are used.  heat is a multiple of 1/8 and the terms are multiples of 2^-31 far
+    // below 2^19, so the scaled terms are exact and their sum is the scaled sum; heat = 1.0 (cold) changes no bit.
+    const double heat = T.heat;
     auto clsAt = [&](int j) __attribute__((always_inline)) { return multi ? (int)gp(gPlaneCls)[gp(gPlane)[j]] : c0; };
     // (two loads behind a branch, not one load through a selected pointer: that would be a flat load, slower than either)
     const double *gTrans = T.ln_trans;
-    auto trn = [&](int cc, int a, int s2) __attribute__((always_inline)) -> double { if (multi) return gp(gTrans)[((int64_t)cc * S + a) * S + s2]; return ldsLoadD(&L.lt[a][s2]); };
+    auto trn = [&](int cc, int a, int s2) __attribute__((always_inline)) -> double { if (multi) return heat * gp(gTrans)[((int64_t)cc * S + a) * S + s2]; return ldsLoadD(&L.lt[a][s2]); };
     // value of state a at base q: from the ring while no base of the block being computed (first base jb) has taken its column,
     // from HBM before
     auto at = [&](int q, int a, int jb) __attribute__((always_inline)) -> double {
@@ -2807,7 +2813,7 @@ AUGX_KFN void forwardPiece(const DevTables &T, const BatchView &B, FwdLds &L, in
     };
     FOR_THREADS(t) {
         for (int i = t; i < WAVE * SP; i += NT) (*lp(&L.ring[i / SP][i % SP])) = AUGX_NINF;
-        for (int i = t; i < SP * SP; i += NT) (*lp(&L.lt[i / SP][i % SP])) = (i / SP < S && i % SP < S) ? lnT(T, c0, i / SP, i % SP) : AUGX_NINF;
+        for (int i = t; i < SP * SP; i += NT) (*lp(&L.lt[i / SP][i % SP])) = (i / SP < S && i % SP < S) ? heat * lnT(T, c0, i / SP, i % SP) : AUGX_NINF;
         if (t < SP) {
             const int k = t < S && T.reachable[t] ? T.kind[t] : -1;
             const bool var = (k >= AUGX_K_SINGLE && k <= AUGX_K_RTERMINAL) || k == AUGX_K_LESSD || k == AUGX_K_RLESSD;
@@ -2883,7 +2889,7 @@ AUGX_KFN void forwardPiece(const DevTables &T, const BatchView &B, FwdLds &L, in
     BLOCK_SYNC();
     FOR_THREADS(t) {
         TX(nxtI) = (t >= WAVE && (uint32_t)(t - WAVE) < (*lp(&L.bCnt[0][0]))) ? ldItem(gItems + (*lp(&L.bOff[0])) + (t - WAVE)) : Item{AUGX_NINF, 0u, 0u};
-        if (t >= NT - BLK * NSIG) { const int i = t - (NT - BLK * NSIG); (*lp(&L.sg[0][i / NSIG][i % NSIG])) = i / NSIG < n ? gp(gSig)[(int64_t)(i / NSIG) * NSIG + i % NSIG] : AUGX_NINF; }
+        if (t >= NT - BLK * NSIG) { const int i = t - (NT - BLK * NSIG); (*lp(&L.sg[0][i / NSIG][i % NSIG])) = i / NSIG < n ? heat * gp(gSig)[(int64_t)(i / NSIG) * NSIG + i % NSIG] : AUGX_NINF; }
     }
     BLOCK_SYNC();
     // a chain state at base j: first what reaches it from the states made in earlier steps of the block (all bases of the block
@@ -3025,7 +3031,7 @@ AUGX_KFN void forwardPiece(const DevTables &T, const BatchView &B, FwdLds &L, in
             if (b + 1 < nBlocks) TX(nxtI) = (t >= WAVE && (uint32_t)(t - WAVE) < (*lp(&L.bCnt[par ^ 1][0]))) ? ldItem(gItems + (*lp(&L.bOff[par ^ 1])) + (t - WAVE)) : Item{AUGX_NINF, 0u, 0u};
             if (b + 1 < nBlocks && t >= NT - BLK * NSIG) { // (the last wavefronts: the first one has the geometric states)
                 const int i = t - (NT - BLK * NSIG), dj = i / NSIG, j = jb + BLK + dj;
-                (*lp(&L.sg[par ^ 1][dj][i % NSIG])) = j < n ? gp(gSig)[(int64_t)j * NSIG + i % NSIG] : AUGX_NINF;
+                (*lp(&L.sg[par ^ 1][dj][i % NSIG])) = j < n ? heat * gp(gSig)[(int64_t)j * NSIG + i % NSIG] : AUGX_NINF;
             }
             if (t >= WAVE && t - WAVE < 7 * BLK) chainOthers((t - WAVE) / BLK, (t - WAVE) % BLK, jb, par);
         }
@@ -3045,7 +3051,7 @@ AUGX_KFN void forwardPiece(const DevTables &T, const BatchView &B, FwdLds &L, in
             double pv;
             if (tag == SRC_COL0) { const int a = (int)(I.src & 0x3Fu); pv = initKind == 0 ? T.ln_init[a] : (a == synch ? 0.0 : AUGX_NINF); }
             else pv = at(eop, tag == SRC_VIG ? igS : (int)(*lp(&L.anc[s2][ai])), jb);
-            return pv + I.te;
+            return pv + heat * I.te;
         };
         auto candidates = [&](uint32_t lo, uint32_t hi) __attribute__((always_inline)) {
             FOR_THREADS(t) {

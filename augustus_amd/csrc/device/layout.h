@@ -374,6 +374,7 @@ inline void fillDevTablesScalars(const augx_tables &t, DevTables &D) {
     D.tss_n = t.tss_n; D.tss_k = t.tss_k; D.tsstata_n = t.tsstata_n; D.tsstata_k = t.tsstata_k; D.tata_n = t.tata_n; D.tata_k = t.tata_k;
     D.tts_n = t.tts_n; D.tts_k = t.tts_k; D.ln_tts_rand = t.ln_tts_rand; D.ln2 = t.ln2;
     D.dense = modelIsDense(t);
+    D.heat = t.heat;
     {   // end-gate bits of the variable-length states: the state index while it fits a 64-bit mask, else a compact numbering
         int nb = 0;
         for (int s = 0; s < t.S; s++) {

@@ -322,6 +322,9 @@ inline void buildOptions(const SamplePiece &P, int s, int j, OptList &L) {
     const int S = P.S, kind = t.state_kind[s];
     const int dssWhole = t.Ds + 2 + t.De, assLag = t.As + 2 + t.Ae + t.U, dL = t.d - 2 - t.De - t.As - 2 - t.U;
     auto Fat = [&](int q, int a) { return q < 0 ? -INFINITY : P.F[(size_t)q * S + a]; };
+    // --temperature: an option is the summand of the forward algorithm, its factor transition x emission heated and the predecessor's
+    // value not (reference optionslist->add(.., fwdsummand), e.g. src/exonmodel.cc:1095-1098) -- term by term as the kernels scale them
+    const double heat = t.heat;
     L.o.clear();
     const bool chain = isChainKind(kind);
     const bool fixed = kind == AUGX_K_LONGDSS || kind == AUGX_K_RLONGDSS || kind == AUGX_K_LONGASS || kind == AUGX_K_RLONGASS ||
@@ -335,7 +338,7 @@ inline void buildOptions(const SamplePiece &P, int s, int j, OptList &L) {
         if (eop >= 0 && emi > -INFINITY)
             for (int ai = 0; ai < t.n_anc[s]; ai++) {
                 const int a = t.anc[s][ai];
-                const double lp = Fat(eop, a) + (P.lnT(j, a, s) + emi);
+                const double lp = Fat(eop, a) + (heat * P.lnT(j, a, s) + heat * emi);
                 if (lp > -INFINITY) L.o.push_back({a, eop, lp});
             }
     } else if (isUtrExonKind(kind)) { // UTR exon: the site list of its window, latest predecessor end first, ancestors in their order
@@ -347,7 +350,7 @@ inline void buildOptions(const SamplePiece &P, int s, int j, OptList &L) {
             if (!utrCand(X, D, idx, te, eop)) continue;
             for (int ai = 0; ai < t.n_anc[s]; ai++) {
                 const int a = t.anc[s][ai];
-                const double lp = Fat(eop > 0 ? eop : 0, a) + (P.lnT(j, a, s) + te);
+                const double lp = Fat(eop > 0 ? eop : 0, a) + (heat * P.lnT(j, a, s) + heat * te);
                 if (lp > -INFINITY) L.o.push_back({a, eop, lp});
             }
         }
@@ -365,7 +368,7 @@ inline void buildOptions(const SamplePiece &P, int s, int j, OptList &L) {
             const Item &I = P.items[i0 + it];
             if ((I.kp >> KEY_BITS) != pid || !(I.te > -INFINITY)) continue;
             const int eop = (int)(I.kp & KEY_MASK) - KEY_BIAS, a = (int)(I.src & 127u);
-            const double lp = Fat(eop > 0 ? eop : 0, a) + I.te;
+            const double lp = Fat(eop > 0 ? eop : 0, a) + heat * I.te;
             if (lp > -INFINITY) L.o.push_back({a, eop, lp});
         }
         int pos[AUGX_MAX_STATES];
@@ -391,7 +394,7 @@ inline void buildOptions(const SamplePiece &P, int s, int j, OptList &L) {
             double pv;
             if (tag == SRC_COL0) { a = (int)(I.src & 0x3Fu); pv = P.F[a]; } // column 0 holds the initial probabilities
             else { a = tag == SRC_VIG ? P.igS : t.anc[s][ai]; pv = Fat(eop, a); }
-            const double lp = pv + I.te;
+            const double lp = pv + heat * I.te;
             if (lp > -INFINITY) L.o.push_back({a, eop, lp});
         }
         // the reference lists them exon start after exon start, the latest first, and for each the ancestors in their order
@@ -446,7 +449,7 @@ inline void memoStep(const SamplePiece &P, int s, int j, OptList *L) {
         if (site >= 0 && then >= 0 && now != then) te = te + (assSiteValue(*P.hT, *P.hB, P.hp, now, q) - assSiteValue(*P.hT, *P.hB, P.hp, then, q));
         for (int ai = 0; ai < t.n_anc[s]; ai++) {
             const int a = t.anc[s][ai];
-            const double lp = P.F[(size_t)col * S + a] + (P.lnT(j, a, s) + te);
+            const double lp = P.F[(size_t)col * S + a] + (t.heat * P.lnT(j, a, s) + t.heat * te);
             if (lp > -INFINITY) L->o.push_back({a, eop2, lp});
         }
     }

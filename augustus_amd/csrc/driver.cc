@@ -873,6 +873,8 @@ extern "C" int augx_main(int argc, const char *const *argv) {
     if (M.speciesSpecificTrans) std::cout << " Using species specific transition matrix: " << M.transFileUsed;
     else std::cout << " Using default transition matrix.";
     std::cout << std::endl;
+    // (reference NAMGene::NAMGene, src/namgene.cc:139-140: after the transition matrix has been read)
+    if (M.temperature && verbosity) std::cout << "# setting temperature to " << M.temperature << " (for sampling)" << std::endl;
 
     std::vector<Record> recs;
     {

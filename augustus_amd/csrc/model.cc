@@ -370,6 +370,21 @@ void Model::load(const std::string &cfgPathIn, const std::string &sp,
     t.d = opt.getInt("/IntronModel/d", 0);
     t.tis_mem = opt.getInt("/ExonModel/tis_motif_memory", 3);
     t.gc_win = opt.getInt("GCwinsize", 10000);
+    {   // --temperature (reference Constant::init, src/types.cc:443-448: an unsigned, clamped to 7 with a note on the error stream)
+        long temp = 0;
+        if (opt.has("temperature")) { // (anything but a whole number is an error: a run meant heated must not come out cold without a word)
+            const std::string &v = opt.get("temperature");
+            char *end = nullptr;
+            temp = strtol(v.c_str(), &end, 10);
+            if (v.empty() || end == v.c_str() || *end) throw ConfigError("temperature must be one of 0 1 2 3 4 5 6 7, not \"" + v + "\"");
+        }
+        temperature = (int)temp;
+        if (temp < 0 || temp > 7) {
+            stderrNotes += "No temperature >7 allowed. temperature must be one of 0 1 2 3 4 5 6 7. Will use temperature=7.\n";
+            temperature = 7;
+        }
+        t.heat = (8.0 - temperature) / 8;
+    }
     // soft-masking: lower-case runs are nonexonpart hints of source RM (reference src/extrinsicinfo.cc:1696-1724); their bonus
     // comes from the extrinsic configuration.  Only the shipped shape of that file is supported: every bonus / malus 1
     // but the RM grade quotient of nonexonpart.

@@ -43,6 +43,7 @@ struct Model {
     std::string transTable;          // 64 amino-acid letters by codon index aaa, aac, ... ttt ('*': stop) of --translation_table
     std::string stderrNotes;         // what the reference writes to its error stream while it reads the parameters
     std::string codeWarnings;        // the lines the reference prints first when the table is not the standard one
+    int temperature = 0;             // --temperature after the reference's clamp to 0..7 (t.heat = (8 - temperature) / 8)
     augx_tables t{};
     // owning storage behind the pointers of t
     std::vector<double> ln_trans, ig_emi, ig_short, in_emi, ex_emi, ex_init, ex_et, ex_pls, tis_motif, ass_motif,

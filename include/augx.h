@@ -173,6 +173,11 @@ typedef struct augx_tables {
     /* Markov order of the intron content table where it is not k (tetrahymena: 3 beside 4; IntronModel::k, the `k` line of the
      * [EMISSION] section of the species' intron file, src/intronmodel.cc:356-372): in_emi is [C][4^(k_in+1)].  Without UTR states only */
     int k_in;
+    /* --temperature=t, t = 0..7 (Constant::temperature, src/types.cc:443-448): heat = (8 - t) / 8, 1.0 when cold.  Every summand of the
+     * forward algorithm and every option of a sampled step carries its factor transition x emission raised to this power
+     * (LLDouble::heated, src/lldouble.cc:209-264) -- in ln: heat * (ln t + ln e).  The predecessor's forward value, the initial and
+     * terminal probabilities and everything of the Viterbi decode are not heated */
+    double heat;
 } augx_tables;
 
 typedef struct augx_model augx_model;     /* host-side immutable model: tables + option values          */
