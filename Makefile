@@ -14,7 +14,7 @@ DEVHDR  = $(SRC)/device/assmemo.h $(SRC)/device/dp.h $(SRC)/device/kernels.h $(S
 HOSTHDR = $(SRC)/model.h $(SRC)/genes.h $(SRC)/capi_internal.h include/augx.h
 
 all: product oracle emu
-product: augustus_amd/libaugx.so augustus_amd/bin/augustus
+product: augustus_amd/libaugx.so augustus_amd/libaugx_smallwin.so augustus_amd/bin/augustus
 
 # The heavy kernel families are translation units of their own, one object per block size (device/launch.h), so that `make -j`
 # compiles them side by side (the whole library: ~1.5 min on 8 cores instead of ~4.5) and a kernel change rebuilds one family.
@@ -41,6 +41,22 @@ $(OBJ)/%.o: $(SRC)/%.cc $(HOSTHDR) $(SRC)/device/layout.h $(SRC)/device/dp.h
 augustus_amd/libaugx.so: $(HOSTOBJS) $(OBJ)/decoder.o $(KOBJS)
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $^
 
+# TEST INFRASTRUCTURE, built with the product because it needs the product's objects and has to travel with them: the library with
+# the trellis kernels built for the smallest LDS windows kernels.h admits (SMALLWIN below; tests/test_gpu_trellis.py loads it through
+# AUGX_LIB; nothing of the product loads or ships it).  It costs three more k_trellis compiles per product build.  Only those three
+# objects depend on the windows: decoder.o and the other families lay out nothing by them (compiled with the flags they differ from the
+# product's objects in the compilation-unit id alone, which hipcc hashes from the options; with -fuse-cuid=none they are the same
+# bytes), so everything else is the product's own object
+SWOBJ = build/obj_smallwin
+define SWRULE
+$(SWOBJ)/k_trellis_$(1).o: $(SRC)/device/k_trellis.hip $(DEVHDR) include/augx.h
+	@mkdir -p $(SWOBJ)
+	$(HIPCC) $(HIPFLAGS) $$(SMALLWIN) -DAUGX_TU_BLK=$(1) -c -o $$@ $$<
+endef
+$(foreach b,8 4 2,$(eval $(call SWRULE,$(b))))
+augustus_amd/libaugx_smallwin.so: $(HOSTOBJS) $(OBJ)/decoder.o $(filter-out $(OBJ)/k_trellis_%,$(KOBJS)) $(foreach b,8 4 2,$(SWOBJ)/k_trellis_$(b).o)
+	$(HIPCC) $(HIPFLAGS) -shared -o $@ $^
+
 # developer builds, objects of their own, loaded instead of the product library when AUGX_LIB names them:
 #   make prof                                   cycle counters of the trellis wavefronts (AUGX_PROF=1) -> augustus_amd/libaugx_prof.so
 #   make variant NAME=x FLAGS="-DAUGX_..."      any other set of build-time switches             -> augustus_amd/libaugx_x.so
@@ -61,7 +77,7 @@ oracle: oracle/libghmm_twin.so
 oracle/libghmm_twin.so: oracle/ghmm_twin.cc include/augx.h
 	$(CXX) $(CXXFLAGS) -shared -o $@ oracle/ghmm_twin.cc
 
-emu: build/libaugx_emu.so build/libaugx_emu_pl1.so build/libaugx_emu_slowq.so
+emu: build/libaugx_emu.so build/libaugx_emu_pl1.so build/libaugx_emu_slowq.so build/libaugx_emu_smallwin.so
 build/libaugx_emu.so: tests/emu/emu.cc $(DEVHDR) include/augx.h
 	@mkdir -p build
 	$(CXX) $(CXXFLAGS) -shared -o $@ tests/emu/emu.cc
@@ -76,9 +92,16 @@ build/libaugx_emu_slowq.so: tests/emu/emu.cc $(DEVHDR) include/augx.h
 	@mkdir -p build
 	$(CXX) $(CXXFLAGS) -DAUGX_SLOWQ_AT=5 -shared -o $@ tests/emu/emu.cc
 
+# the same emulator with the smallest LDS windows of the trellis that kernels.h admits (its static_asserts next to ITEM_CAP): the reads
+# of predecessor values back from HBM and the candidates beyond the LDS staging, rare in the product, are then the common case
+SMALLWIN = -DAUGX_ITEM_CAP=1024 -DAUGX_LIST_WIN=128 -DAUGX_VIG_WIN=128
+build/libaugx_emu_smallwin.so: tests/emu/emu.cc $(DEVHDR) include/augx.h
+	@mkdir -p build
+	$(CXX) $(CXXFLAGS) $(SMALLWIN) -shared -o $@ tests/emu/emu.cc
+
 ref:
 	$(MAKE) -C oracle -j8
 
 clean:
-	rm -rf build augustus_amd/libaugx.so augustus_amd/bin oracle/libghmm_twin.so
+	rm -rf build augustus_amd/libaugx.so augustus_amd/libaugx_smallwin.so augustus_amd/bin oracle/libghmm_twin.so
 .PHONY: all product prof variant oracle emu ref clean

@@ -74,6 +74,11 @@ struct Item {
 // of them can move the difference of two alternative paths by up to ~1e-7, so the reference -- which rounds differently -- may decide such a
 // cell the other way.  The back-trace counts the cells on the chosen path where that can have happened.
 constexpr double AUGX_NEAR_TIE = 2e-7;
+// fixed-point sums of the forward kernels (kernels.h: forwardPiece, dense.h): 1.0 = 2^FWD_FIX_BITS, so that 64 bits hold FWD_SUM_TERMS terms
+// of at most 1.0 -- more than any cell of an admitted model has candidates (layout.h: checkForwardSum)
+constexpr int FWD_FIX_BITS = 46;
+constexpr double FWD_FIX = (double)(1ull << FWD_FIX_BITS);
+constexpr long long FWD_SUM_TERMS = 1ll << (64 - FWD_FIX_BITS);
 constexpr int KEY_BITS = 22;                 // pieces on the device path are shorter than 2^22 bases
 constexpr uint32_t KEY_MASK = (1u << KEY_BITS) - 1;
 constexpr int KEY_BIAS = 64;                 // key = eop + KEY_BIAS >= 0 (eop >= -(3 + W) - 1 for a left-truncated initial exon)

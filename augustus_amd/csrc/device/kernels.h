@@ -536,6 +536,55 @@ enum EmuCand {
     EC_N
 };
 static long long g_emuCand[EC_N] = {0};
+// data paths of the trellis, of its segment bookkeeping and of the forward kernel that the emulated pieces took
+// (tests/test_emu_trellis.py: the inputs of helpers.trellis_edge_cases must reach every one of them; helpers.TRELLIS_COVERAGE names
+// them in this order).  Four consecutive entries "per list": sel 0 laVal, 1 lrVal, 2 ldVal, 3 rdVal
+enum EmuTrellis {
+    ET_CHUNK_HBM,         // trellisItems: chunks of 64 candidates read from HBM (not all of them below ITEM_CAP)
+    ET_CHUNK_STRADDLE,    //   of them the chunk that begins below ITEM_CAP and ends beyond it
+    ET_SLOW_LIST,         // [4] list values read back from HBM, per list
+    ET_SLOW_VIG = ET_SLOW_LIST + 4, // igenic values read back from HBM
+    ET_PAY_TOP,           // [4] candidates with pay == top (the newest entry read back), per list
+    ET_PAY_TOP1 = ET_PAY_TOP + 4,   // [4] pay == top + 1 (the oldest entry taken from LDS), per list
+    ET_PAY_VIGLO = ET_PAY_TOP1 + 4, // igenic candidates with pay == vigLo
+    ET_PAY_VIGLO1,        //   with pay == vigLo + 1
+    ET_SLOW_DEAD,         // values read back in a run that starts dead (pass 1 of a later segment)
+    ET_SLOW_DEAD_CUT,     //   of them the ones the dead start replaces (they lie before the segment)
+    ET_SLOW_MODE1,        // values read back by a fix-up (MODE 1)
+    ET_SLOW_MODE2,        //   by a continuation of pass 3 (MODE 2)
+    ET_SLOW_MODE3,        //   by the last, non-comparing pass (MODE 3)
+    ET_SLOW_PAST_JUMP,    // igenic values read back from before a run of N that the same run jumped over
+    ET_SLOW_MULTI,        // values read back in a piece with several GC classes
+    ET_LIST_PAST_JUMP,    // list values (LDS or HBM) of entries older than a jump of the same run
+    ET_FLUSH_CMP,         // loadTileThread: list values retired by a comparing pass
+    ET_FLUSH_CMP_BAD,     //   that differed from pass 1 by something else than the tile's offset
+    ET_LONGV_READ,        // long-lag cells staged from HBM (dStateLen >= WAVE)
+    ET_TILE_FULL,         // tiles with ITEM_CAP or more candidates (the LDS staging is full)
+    ET_JUMP_RESTAGE,      // trellisPiece: jumps (each re-stages the tile it lands on and fills vigw with the run's igenic column)
+    ET_FIX_CONVERGED,     // fix-ups (MODE 1) that converged
+    ET_FIX_GAVEUP,        //   that gave up at their limit
+    ET_P3_CONVERGED,      // continuations (MODE 2) that converged
+    ET_P3_AT_SEAM,        //   tiles at which one would have stopped but for the seam of another run
+    ET_P3_TO_END,         //   that reached the end of the piece
+    ET_M3_TILES,          // tiles computed by the last pass (MODE 3)
+    ET_FIN_OVERRUN,       // segFinalizePiece: seams a later continuation ran over (continue)
+    ET_FIN_COVERED,       //   continuations that extended `covered`
+    ET_FIN_TO_END,        //   runs that reached the end of the piece (break)
+    ET_FIN_SEAM,          //   seams recorded
+    ET_FWD_GT_NTW,        // forwardPiece: blocks with more candidates than threads (cntAll > NTW)
+    ET_FWD_NONRT_GT_NTW,  //   with more candidates that are not RTERMINAL than threads (step E starts beyond NTW)
+    ET_FWD_AT_HBM,        //   predecessors older than the ring, read from HBM
+    ET_FWD_MAX_CELL,      //   largest number of live candidates summed into one cell (a maximum, not a count)
+    ET_FWD_MAX_SUM,       //   largest fixed-point sum of one cell in units of 1.0 = FWD_FIX, rounded up (a maximum; FWD_SUM_TERMS is what 64 bits hold)
+    ET_FWD_TRN_MULTI,     //   transition terms fetched from HBM (piece with several GC classes)
+    ET_FWD_TRN_SINGLE,    //   from LDS
+    ET_FWD_COL0,          //   candidates that start in column 0
+    ET_FWD_HEATED_OVER,   //   candidates beyond the first NTW of a block evaluated with heat != 1
+    ET_N
+};
+static long long g_emuTrellis[ET_N] = {0};
+static int g_emuMode = 0, g_emuJumpS = -1, g_emuJumpCnt[4] = {0, 0, 0, 0}; // the run being emulated: MODE, the bases its last jump skipped, the list counts before it
+static int g_emuFwdCell[8][64]; // forwardPiece: live candidates per cell of the current block
 #endif
 struct VarDesc { // 64 bytes (kind, frame and geometry of the state are per-state constants: VarConst)
     int8_t pl;              // plane (GC class) of the end base j: selects every class-dependent array
@@ -1357,6 +1406,22 @@ AUGX_KFN void candWorkgroup(const DevTables &T, const BatchView &B, CandLds &L, 
 constexpr int NWORK = 3, W_C = 3, W_X = 4, W_I = 5, W_LOAD = 6; // trellis workgroup: wavefronts 0..2 workers (near / late fixed-lag states + candidates), 3 geometric states, 4 far fixed-lag states, 5 igenic, 6.. loaders
 constexpr int LOAD_T = (8 - W_LOAD) * WAVE;                     // threads of the loader wavefronts
 constexpr int ITEM_CAP = AUGX_ITEM_CAP;   // candidates of one tile staged in LDS (the rest, if any, is read from HBM; a tile of random DNA has ~940)
+// list entries at or below (newest entry of the block) - (LIST_WIN - LIST_AHEAD) are read back from HBM (trellisItems): the far
+// fixed-lag wavefront runs up to two blocks = LIST_AHEAD entries ahead of the workers
+constexpr int LIST_AHEAD = 32;
+// What the three window constants (dp.h: AUGX_ITEM_CAP, AUGX_LIST_WIN, AUGX_VIG_WIN) must satisfy.  The windows are indexed with a mask.
+// A value read back from HBM must have been retired at least one tile barrier ago, i.e. belong to tile - 2 or older, and a value
+// that is retired while tile `tile` is computed (tile - 1: loadTileThread, flushBpThread) must still be in its window:
+// - igenic: a worker reads back bases <= jb - 1 - VIG_WIN, jb <= tile * WAVE + WAVE - 1: tile - 2 or older from VIG_WIN = 2 * WAVE on;
+//   then the window also holds tile - 1 while the igenic wavefront writes tile
+// - lists: a site is a dinucleotide (or base 0), so a list gains at most WAVE / 2 + 1 entries per tile.  Tile - 1, tile and the far
+//   wavefront's lead hold at most WAVE + 1 + LIST_AHEAD of them: the window must hold those, and an entry read back (LIST_WIN - LIST_AHEAD
+//   or more entries old) must be older than the WAVE + 1 of tile - 1 and tile -- one and the same inequality
+// - the jump over a run of N keeps NT * 8 partial sums in the space of the staged candidates
+static_assert((ITEM_CAP & (ITEM_CAP - 1)) == 0 && (LIST_WIN & (LIST_WIN - 1)) == 0 && (VIG_WIN & (VIG_WIN - 1)) == 0, "the windows are indexed with a mask: powers of two");
+static_assert(LIST_WIN - LIST_AHEAD >= WAVE + 1, "LIST_WIN: a value read back was retired a tile barrier ago; one retired is still there");
+static_assert(VIG_WIN >= 2 * WAVE, "VIG_WIN: a value read back was retired a tile barrier ago; one retired is still there");
+static_assert(ITEM_CAP % WAVE == 0 && sizeof(Item) * 2 * ITEM_CAP >= sizeof(double) * NT * 8, "ITEM_CAP: whole chunks; scratch of the jump");
 
 struct TrellisLds {
     double ring[WAVE][SP];          // ln V of the last 64 columns, [j & 63][state]
@@ -1539,6 +1604,9 @@ AUGX_KFN void loadTileThread(const TrellisCtx &X, int tile, int buf, int tid, in
     for (int k = 0; k < KEQ; k++) {
         const int i = tid + k * nth, q = j0 + i / 6;
         vEq[k] = (i < WAVE * 6 && dL >= WAVE && q - dL >= X.segLo && q < n) ? ldCoherent(&B.longV[(g0 - dL) * 6 + i]) : AUGX_NINF;
+#ifdef AUGX_EMU
+        g_emuTrellis[ET_LONGV_READ] += i < WAVE * 6 && dL >= WAVE && q - dL >= X.segLo && q < n;
+#endif
     }
     // block tables: thread i <= NB the first candidate of block i, i < 3 NB the split points, i < 4 NB the newest list entries
     int32_t vOff = 0;
@@ -1561,6 +1629,9 @@ AUGX_KFN void loadTileThread(const TrellisCtx &X, int tile, int buf, int tid, in
     // (the candidate records go through registers in two halves: they are most of the tile's bytes)
     constexpr int KI = (ITEM_CAP + LOAD_T - 1) / LOAD_T, KH = (KI + 1) / 2;
     const int cntI = lastI - firstI < (uint64_t)ITEM_CAP ? (int)(lastI - firstI) : ITEM_CAP;
+#ifdef AUGX_EMU
+    g_emuTrellis[ET_TILE_FULL] += tid == 0 && cntI == ITEM_CAP;
+#endif
     Item vItem[KH];
     const Item *gi = B.items + firstI;
 #pragma unroll
@@ -1586,6 +1657,9 @@ AUGX_KFN void loadTileThread(const TrellisCtx &X, int tile, int buf, int tid, in
 #pragma unroll
                         for (int f = 0; f < 3; f++) bad |= !(L.lcVal[sel][si & (LIST_WIN - 1)][f] == gp(a)[(X.lo + si) * 3 + f] + dT);
                         if (bad) ldsMaxI(&L.lastBad, tile - 2);
+#ifdef AUGX_EMU
+                        g_emuTrellis[ET_FLUSH_CMP]++; g_emuTrellis[ET_FLUSH_CMP_BAD] += bad;
+#endif
                     }
 #pragma unroll
                     for (int f = 0; f < 3; f++) gp(a)[(X.lo + si) * 3 + f] = L.lcVal[sel][si & (LIST_WIN - 1)][f];
@@ -1654,8 +1728,7 @@ AUGX_KFN void trellisItems(TrellisCtx &X, int w, int buf, int blk, int jb, int l
     const int S = X.S;
     const uint64_t tileItem0 = L.tileItem0[buf];
     // list entries at or below topK have (or may have: the far fixed-lag wavefront runs up to two blocks = LIST_AHEAD
-    // entries ahead) left the LDS cache of the newest LIST_WIN entries
-    constexpr int LIST_AHEAD = 32;
+    // entries ahead, see ITEM_CAP above) left the LDS cache of the newest LIST_WIN entries
     const int top0 = L.listTop[buf][blk][0] - (LIST_WIN - LIST_AHEAD), top1 = L.listTop[buf][blk][1] - (LIST_WIN - LIST_AHEAD),
               top2 = L.listTop[buf][blk][2] - (LIST_WIN - LIST_AHEAD), top3 = L.listTop[buf][blk][3] - (LIST_WIN - LIST_AHEAD);
     // The cell of a (base, state) pair is the maximum over the pair's candidates, which may sit in any lanes of any chunks of
@@ -1665,6 +1738,9 @@ AUGX_KFN void trellisItems(TrellisCtx &X, int w, int buf, int blk, int jb, int l
     PROF_MARK(X, 7);
     for (int base = lo; base < hi; base += WAVE) {
         const bool inLds = base + WAVE <= ITEM_CAP;
+#ifdef AUGX_EMU
+        g_emuTrellis[ET_CHUNK_HBM] += !inLds; g_emuTrellis[ET_CHUNK_STRADDLE] += !inLds && base < ITEM_CAP;
+#endif
         FOR_WLANES(t, w) {
             const int l = t & 63, it = base + l;
             const bool valid = it < hi;
@@ -1682,6 +1758,19 @@ AUGX_KFN void trellisItems(TrellisCtx &X, int w, int buf, int blk, int jb, int l
 #ifdef AUGX_EMU
             if (l == 0) g_emuItemWaves++;
             if (slow) { if (tag == SRC_LIST) g_emuSlowList++; else g_emuSlowVig++; }
+            if (valid && tag == SRC_LIST) {
+                g_emuTrellis[ET_SLOW_LIST + sel] += slow; g_emuTrellis[ET_PAY_TOP + sel] += pay == top; g_emuTrellis[ET_PAY_TOP1 + sel] += pay == top + 1;
+                g_emuTrellis[ET_LIST_PAST_JUMP] += g_emuJumpS >= 0 && pay < g_emuJumpCnt[sel];
+            }
+            if (valid && tag == SRC_VIG) {
+                g_emuTrellis[ET_SLOW_VIG] += slow; g_emuTrellis[ET_PAY_VIGLO] += pay == vigLo; g_emuTrellis[ET_PAY_VIGLO1] += pay == vigLo + 1;
+                g_emuTrellis[ET_SLOW_PAST_JUMP] += slow && g_emuJumpS >= 0 && pay < g_emuJumpS;
+            }
+            if (slow) {
+                g_emuTrellis[ET_SLOW_DEAD] += X.dead; g_emuTrellis[ET_SLOW_MULTI] += X.multi;
+                g_emuTrellis[ET_SLOW_DEAD_CUT] += X.dead && (tag == SRC_LIST ? pay < X.listLo[sel] : pay <= X.anchor);
+                if (g_emuMode >= 1) g_emuTrellis[ET_SLOW_MODE1 + g_emuMode - 1]++;
+            }
 #endif
             if (slow) { // the value left the LDS windows long ago: read it back from HBM
                 if (tag == SRC_LIST) {
@@ -1724,6 +1813,9 @@ AUGX_KFN void trellisPiece(const DevTables &T, const BatchView &B, TrellisLds &L
         tStart = -2 - B.segStop[segIdx] + 1;
         ckSrc = segIdx * 2 + 1;
     }
+#ifdef AUGX_EMU
+    g_emuMode = MODE; g_emuJumpS = -1;
+#endif
     const SegDesc sd = B.segs[segIdx];
     const int p = sd.piece;
     TrellisCtx X(T, B, L, p);
@@ -2440,6 +2532,9 @@ AUGX_KFN void trellisPiece(const DevTables &T, const BatchView &B, TrellisLds &L
         BLOCK_GLOBAL_SYNC(); // stores of this tile are visible to later (coherent) loads; the staged tile is complete
         FOR_WAVES(w) { if (w == 0) PROF_TSTAMP(X, tile == 124, 15); }
         tLast = tile;
+#ifdef AUGX_EMU
+        g_emuTrellis[ET_M3_TILES] += MODE == 3;
+#endif
         if (B.ckCol) { // ---- pieces cut into segments: the column at the end of the tile (complete: every wavefront has passed the barrier)
             FOR_THREADS(t) {
                 if (t < SP) {
@@ -2477,6 +2572,11 @@ AUGX_KFN void trellisPiece(const DevTables &T, const BatchView &B, TrellisLds &L
                     if (e == tile || e == tile - 1) atSeam = true;
                 }
             }
+#ifdef AUGX_EMU
+            if (lb < needTile && (tile - 1) - lb >= win) g_emuTrellis[atSeam ? ET_P3_AT_SEAM : MODE == 1 ? ET_FIX_CONVERGED : ET_P3_CONVERGED]++;
+            else if (MODE == 1 && tile + 1 == tEnd) g_emuTrellis[ET_FIX_GAVEUP]++;
+            else if (MODE == 2 && tile + 1 == tEnd) g_emuTrellis[ET_P3_TO_END]++;
+#endif
             if (lb < needTile && (tile - 1) - lb >= win && !atSeam) break;
             if (MODE == 1 && tile + 1 == tEnd) gaveUp = true;
         }
@@ -2587,6 +2687,8 @@ AUGX_KFN void trellisPiece(const DevTables &T, const BatchView &B, TrellisLds &L
                 {
 #ifdef AUGX_EMU
                     g_emuJumpTiles += tJ - (tile + 1); g_emuJumps++;
+                    g_emuTrellis[ET_JUMP_RESTAGE]++; g_emuJumpS = jS;
+                    for (int i = 0; i < 4; i++) g_emuJumpCnt[i] = (int)B.cnt[fidx(o + 1 + jS - 1, CNT_LA + i, NCNT)];
 #endif
                     FOR_THREADS(t) {
                         const int qa = jS + t * per, qb = jS + (t + 1) * per < jE ? jS + (t + 1) * per : jE;
@@ -2751,10 +2853,12 @@ inline void ldsAddU(unsigned long long *p, unsigned long long v) { *p += v; }
 #else
 __device__ inline void ldsAddU(unsigned long long *p, unsigned long long v) { __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); } // ds_add_u64
 #endif
-// the sum over the candidates of a cell is taken in fixed point (terms in (0, 1], 2^-52 apart; < 2048 of them): integer adds
+// the sum over the candidates of a cell is taken in fixed point (terms in (0, 1], 2^-46 apart: dp.h, FWD_FIX): integer adds
 // commute, so the result does not depend on the order the wavefronts' atomics arrive in -- the same forward matrix, hence the
-// same sampled paths, run after run
-constexpr double FWD_FIX = 4503599627370496.0; // 2^52
+// same sampled paths, run after run.  The sum cannot wrap: a term is at most 1.0 = FWD_FIX, and a cell has at most one candidate per
+// ancestor and predecessor base, AUGX_MAX_ANC * (longest exon or intron + 1) <= FWD_SUM_TERMS of them (layout.h: checkForwardSum
+// refuses a model with more).  The count is not idle: ATG (CAG)x3990 GTAAGT puts 3990 live candidates into one cell, and at
+// --temperature=7 their terms are flat enough to sum to 217 (tests/test_emu_trellis.py: EmuTrellis ET_FWD_MAX_SUM)
 struct FwdLds {
     double ring[WAVE][SP];   // ln F of the last 64 columns, [j & 63][state]
     double cmax[8][SP];      // variable-length cells of the current block: largest candidate ...
@@ -2803,12 +2907,21 @@ AUGX_KFN void forwardPiece(const DevTables &T, const BatchView &B, FwdLds &L, in
     auto clsAt = [&](int j) __attribute__((always_inline)) { return multi ? (int)gp(gPlaneCls)[gp(gPlane)[j]] : c0; };
     // (two loads behind a branch, not one load through a selected pointer: that would be a flat load, slower than either)
     const double *gTrans = T.ln_trans;
-    auto trn = [&](int cc, int a, int s2) __attribute__((always_inline)) -> double { if (multi) return heat * gp(gTrans)[((int64_t)cc * S + a) * S + s2]; return ldsLoadD(&L.lt[a][s2]); };
+    auto trn = [&](int cc, int a, int s2) __attribute__((always_inline)) -> double {
+#ifdef AUGX_EMU
+        g_emuTrellis[multi ? ET_FWD_TRN_MULTI : ET_FWD_TRN_SINGLE]++;
+#endif
+        if (multi) return heat * gp(gTrans)[((int64_t)cc * S + a) * S + s2];
+        return ldsLoadD(&L.lt[a][s2]);
+    };
     // value of state a at base q: from the ring while no base of the block being computed (first base jb) has taken its column,
     // from HBM before
     auto at = [&](int q, int a, int jb) __attribute__((always_inline)) -> double {
         if (q < 0) return AUGX_NINF;
         if (jb + BLK - 1 - q < WAVE) return ldsLoadD(&L.ring[q & 63][a]);
+#ifdef AUGX_EMU
+        g_emuTrellis[ET_FWD_AT_HBM]++;
+#endif
         return ldCoherent(&F[(int64_t)q * S + a]);
     };
     FOR_THREADS(t) {
@@ -3043,12 +3156,19 @@ AUGX_KFN void forwardPiece(const DevTables &T, const BatchView &B, FwdLds &L, in
         //      candidate of every cell, the sum around it, the cell
         const uint64_t i0 = (*lp(&L.bOff[par]));
         const uint32_t cntAll = (*lp(&L.bCnt[par][0])), cntNonRT = (*lp(&L.bCnt[par][1]));
+#ifdef AUGX_EMU
+        g_emuTrellis[ET_FWD_GT_NTW] += cntAll > (uint32_t)NTW; g_emuTrellis[ET_FWD_NONRT_GT_NTW] += cntNonRT > (uint32_t)NTW && cntAll > cntNonRT;
+        for (int i = 0; i < 8 * 64; i++) g_emuFwdCell[i / 64][i % 64] = 0;
+#endif
         auto candValue = [&](const Item &I, int &dj, int &s2) __attribute__((always_inline)) -> double {
             dj = (int)(I.kp >> (KEY_BITS + 6)); s2 = (int)((I.kp >> KEY_BITS) & 63);
             if (!(I.te > AUGX_NINF)) return AUGX_NINF;
             const uint32_t tag = I.src >> 30;
             const int ai = (int)((I.src >> 28) & 3), eop = (int)(I.kp & KEY_MASK) - KEY_BIAS;
             double pv;
+#ifdef AUGX_EMU
+            g_emuTrellis[ET_FWD_COL0] += tag == SRC_COL0;
+#endif
             if (tag == SRC_COL0) { const int a = (int)(I.src & 0x3Fu); pv = initKind == 0 ? T.ln_init[a] : (a == synch ? 0.0 : AUGX_NINF); }
             else pv = at(eop, tag == SRC_VIG ? igS : (int)(*lp(&L.anc[s2][ai])), jb);
             return pv + heat * I.te;
@@ -3068,10 +3188,17 @@ AUGX_KFN void forwardPiece(const DevTables &T, const BatchView &B, FwdLds &L, in
             }
             BLOCK_SYNC();
             FOR_THREADS(t) {
+#ifdef AUGX_EMU
+                if (TX(cv) > AUGX_NINF && ++g_emuFwdCell[TX(cdj)][TX(cs2)] > g_emuTrellis[ET_FWD_MAX_CELL]) g_emuTrellis[ET_FWD_MAX_CELL] = g_emuFwdCell[TX(cdj)][TX(cs2)];
+#endif
                 if (TX(cv) > AUGX_NINF) ldsAddU(&L.csum[TX(cdj)][TX(cs2)], (unsigned long long)(exp(TX(cv) - (*lp(&L.cmax[TX(cdj)][TX(cs2)]))) * FWD_FIX));
                 for (uint32_t it = (lo > (uint32_t)NTW ? lo : (uint32_t)NTW) + (uint32_t)(t - WAVE); t >= WAVE && it < hi; it += NTW) {
                     int dj, s2;
                     const double v = candValue(ldItem(gItems + i0 + it), dj, s2);
+#ifdef AUGX_EMU
+                    g_emuTrellis[ET_FWD_HEATED_OVER] += heat != 1.0 && v > AUGX_NINF;
+                    if (v > AUGX_NINF && ++g_emuFwdCell[dj][s2] > g_emuTrellis[ET_FWD_MAX_CELL]) g_emuTrellis[ET_FWD_MAX_CELL] = g_emuFwdCell[dj][s2];
+#endif
                     if (v > AUGX_NINF) ldsAddU(&L.csum[dj][s2], (unsigned long long)(exp(v - (*lp(&L.cmax[dj][s2]))) * FWD_FIX));
                 }
             }
@@ -3083,6 +3210,9 @@ AUGX_KFN void forwardPiece(const DevTables &T, const BatchView &B, FwdLds &L, in
                     const int dj = i / SP, s2 = i % SP, j = jb + dj;
                     if (j >= 1 && j < n) {
                         if ((*lp(&L.cellKind[s2])) == (rt ? 2 : 1)) {
+#ifdef AUGX_EMU
+                            { const long long u = (long long)((L.csum[dj][s2] >> FWD_FIX_BITS) + 1); if (L.csum[dj][s2] && u > g_emuTrellis[ET_FWD_MAX_SUM]) g_emuTrellis[ET_FWD_MAX_SUM] = u; }
+#endif
                             const double f = (*lp(&L.csum[dj][s2])) > 0ull ? (*lp(&L.cmax[dj][s2])) + log((double)(*lp(&L.csum[dj][s2])) / FWD_FIX) : AUGX_NINF;
                             (*lp(&L.ring[j & 63][s2])) = f;
                             if (f > AUGX_NINF) gp(F)[(int64_t)j * S + s2] = f;
@@ -3162,6 +3292,10 @@ AUGX_KFN void segFinalizePiece(const BatchView &B, int p) {
         int endTile = st >= -1 ? st : B.segStop2[s0 + k];
         const double D = st >= -1 ? B.segD[s0 + k] : B.segD2[s0 + k];
         if (st < -1 && endTile < 0) { abortAny = true; endTile = lastTile; } // (never expected: the last pass leaves no fix-up behind)
+#ifdef AUGX_EMU
+        if (endTile < covered - 1) g_emuTrellis[ET_FIN_OVERRUN]++;
+        else { g_emuTrellis[ET_FIN_COVERED] += st < -1 && endTile > covered; g_emuTrellis[endTile >= lastTile ? ET_FIN_TO_END : ET_FIN_SEAM]++; }
+#endif
         if (endTile < covered - 1) continue; // a later continuation ran over this seam: its own offset is relative to what lies behind
         if (st < -1 && endTile > covered) covered = endTile;
         if (endTile >= lastTile) break;     // the run reached the end of the piece: one last region in the frame it started in

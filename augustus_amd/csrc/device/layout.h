@@ -199,7 +199,23 @@ struct BatchSizes {
     }
 };
 
+// a forward cell sums one term of at most 1.0 per candidate in 64-bit fixed point (dp.h: FWD_FIX).  A candidate is a predecessor state
+// (at most AUGX_MAX_ANC ancestors) at a predecessor base (within the longest exon or intron of the model): with no more than
+// FWD_SUM_TERMS of them the sum cannot wrap, whatever their values
+inline long long forwardCellCandidates(const augx_tables &t) {
+    int len = t.max_exon_len > t.d ? t.max_exon_len : t.d;
+    if (t.utr_max_exon_len > len) len = t.utr_max_exon_len;
+    if (t.utr_max3single > len) len = t.utr_max3single;
+    if (t.utr_max3term > len) len = t.utr_max3term;
+    return (long long)AUGX_MAX_ANC * ((long long)len + 1);
+}
+static_assert((long long)AUGX_MAX_ANC * (0x3FFF + 1) <= FWD_SUM_TERMS, "the lengths 14-bit back pointers admit fit the forward sum");
+inline void checkForwardSum(const augx_tables &t) {
+    if (forwardCellCandidates(t) > FWD_SUM_TERMS) throw std::runtime_error("augx: exon or intron lengths too large for the fixed-point sums of the forward pass");
+}
+
 inline void checkModelSupported(const augx_tables &t, int BLK) {
+    checkForwardSum(t);
     if (t.S > SP) throw std::runtime_error("augx: model has more than 48 states: not for the wavefront layout of the trellis kernel (models with UTR states or two intergenic states go to the dense kernels, modelIsDense below)");
     int dL = t.d - 2 - t.De - t.As - 2 - t.U;
     if (dL >= LONG_RING || dL <= BLK || (dL > WAVE - BLK && dL < WAVE)) throw std::runtime_error("augx: intron d out of the supported range");
@@ -296,6 +312,7 @@ inline bool modelIsDense(const augx_tables &t) {
 // the stage order of densePiece (fixed-lag states, early chains, candidates, late chains, reverse terminal exons)
 inline int chooseDenseBlock(const augx_tables &t) {
     if (t.S > SPX) throw std::runtime_error("augx: too many states");
+    checkForwardSum(t);
     const int dssWhole = t.Ds + 2 + t.De, assLag = t.As + 2 + t.Ae + t.U, dL = t.d - 2 - t.De - t.As - 2 - t.U;
     int lag = dssWhole < assLag ? dssWhole : assLag;
     if (dL < lag) lag = dL;

@@ -431,6 +431,20 @@ long long emu_quiet_tiles() { return g_emuQuietTiles; } // (tests: the chain-onl
 int emu_cand_coverage(long long *out) { for (int i = 0; i < EC_N; i++) out[i] = g_emuCand[i]; return EC_N; }
 void emu_cand_coverage_reset() { for (int i = 0; i < EC_N; i++) g_emuCand[i] = 0; }
 int emu_slowq_at() { return SLOWQ_AT; }
+// data paths of the trellis, the segment bookkeeping and the forward kernel taken since the last reset (kernels.h: EmuTrellis, ET_N
+// entries; ET_FWD_MAX_CELL is a maximum)
+int emu_trellis_coverage(long long *out) { for (int i = 0; i < ET_N; i++) out[i] = g_emuTrellis[i]; return ET_N; }
+void emu_trellis_coverage_reset() { for (int i = 0; i < ET_N; i++) g_emuTrellis[i] = 0; }
+// lengths of the model the conditions of the tests rest on: intron d, maxexonlength, W, dStateLen as the kernels get it
+// (layout.h: fillDevTablesScalars), the GC classes, and the most candidates one forward cell can have (layout.h: forwardCellCandidates)
+void emu_model_dims(const augx_tables *t, long long *out) {
+    DevTables D;
+    fillDevTablesScalars(*t, D);
+    out[0] = t->d; out[1] = t->max_exon_len; out[2] = t->W; out[3] = D.dStateLen; out[4] = t->n_classes; out[5] = forwardCellCandidates(*t);
+}
+// the build-time windows of the trellis (dp.h: AUGX_ITEM_CAP, AUGX_LIST_WIN, AUGX_VIG_WIN), what trellisItems and forwardPiece derive
+// from the build (LIST_AHEAD, NTW), and the terms of 1.0 a fixed-point forward sum holds (dp.h: FWD_SUM_TERMS)
+void emu_trellis_windows(int *out) { out[0] = ITEM_CAP; out[1] = LIST_WIN; out[2] = VIG_WIN; out[3] = LIST_AHEAD; out[4] = NT - WAVE; out[5] = (int)FWD_SUM_TERMS; }
 // block size of the candidate / trellis kernels that a decode of this model takes (layout.h; AUGX_BLK applies), -1: unsupported
 int emu_block_size(const augx_tables *t) {
     try { return chooseBlockSize(*t); } catch (std::exception &) { return -1; }

@@ -798,3 +798,103 @@ def prep_first_diff(got, want):
     first = tuple(int(x) for x in bad[0])
     return "%d of %d values differ, first at position %d field %d: %r against %r" % (
         len(bad), a.size, first[0], first[1] if len(first) > 1 else 0, np.atleast_1d(got)[first], np.atleast_1d(want)[first])
+
+
+# ---------------------------------------------------------------------------------------------------
+# the far-window and overflow paths of the trellis and forward kernels (tests/test_emu_trellis.py, tests/test_gpu_trellis.py)
+# ---------------------------------------------------------------------------------------------------
+# kernels.h: EmuTrellis, in the order of the emulator's counters ("*_0".."*_3": per list, sel 0 laVal, 1 lrVal, 2 ldVal, 3 rdVal)
+TRELLIS_COVERAGE = (("chunk_hbm", "chunk_straddle") + tuple("slow_list_%d" % i for i in range(4)) + ("slow_vig",)
+                    + tuple("pay_top_%d" % i for i in range(4)) + tuple("pay_top1_%d" % i for i in range(4))
+                    + ("pay_viglo", "pay_viglo1", "slow_dead", "slow_dead_cut", "slow_mode1", "slow_mode2", "slow_mode3", "slow_past_jump",
+                       "slow_multi", "list_past_jump", "flush_cmp", "flush_cmp_bad", "longv_read", "tile_full", "jump_restage",
+                       "fix_converged", "fix_gaveup", "p3_converged", "p3_at_seam", "p3_to_end", "m3_tiles", "fin_overrun", "fin_covered",
+                       "fin_to_end", "fin_seam", "fwd_gt_ntw", "fwd_nonrt_gt_ntw", "fwd_at_hbm", "fwd_max_cell", "fwd_max_sum",
+                       "fwd_trn_multi", "fwd_trn_single", "fwd_col0", "fwd_heated_over"))
+SMALLWIN_EMU_LIB = os.path.join(ROOT, "build", "libaugx_emu_smallwin.so")
+SMALLWIN_LIB = os.path.join(ROOT, "augustus_amd", "libaugx_smallwin.so")
+
+
+def emu_trellis_coverage(lib=None, reset=False):
+    """{counter: value} of the data paths the trellis, its segment bookkeeping and the forward kernel took in the emulator `lib` since
+    its last reset (fwd_max_cell, fwd_max_sum: maxima); reset=True clears them afterwards"""
+    E = _emu_of(lib)
+    out = (ctypes.c_longlong * 128)()
+    n = E.emu_trellis_coverage(out)
+    assert n == len(TRELLIS_COVERAGE), n
+    if reset:
+        E.emu_trellis_coverage_reset()
+    return dict(zip(TRELLIS_COVERAGE, out[:n]))
+
+
+def emu_trellis_coverage_reset(lib=None):
+    _emu_of(lib).emu_trellis_coverage_reset()
+
+
+def emu_trellis_windows(lib=None):
+    """the trellis windows the emulator `lib` was built with: {ITEM_CAP, LIST_WIN, VIG_WIN, LIST_AHEAD, NTW} (kernels.h), and
+    FWD_SUM_TERMS, the terms of 1.0 a fixed-point sum of the forward kernels holds (dp.h)"""
+    out = (ctypes.c_int * 8)()
+    _emu_of(lib).emu_trellis_windows(out)
+    return dict(zip(("ITEM_CAP", "LIST_WIN", "VIG_WIN", "LIST_AHEAD", "NTW", "FWD_SUM_TERMS"), out[:6]))
+
+
+def revcomp(s):
+    return s[::-1].translate(str.maketrans("ACGTacgt", "TGCAtgca"))
+
+
+def emu_model_dims(tables_ptr, lib=None):
+    """{d, max_exon_len, W, dStateLen, n_classes, fwd_cell_candidates} of a loaded model (include/augx.h: augx_tables; dStateLen as
+    the kernels get it; fwd_cell_candidates: the most candidates one forward cell can have, layout.h: forwardCellCandidates)"""
+    out = (ctypes.c_longlong * 8)()
+    _emu_of(lib).emu_model_dims(tables_ptr, out)
+    return dict(zip(("d", "max_exon_len", "W", "dStateLen", "n_classes", "fwd_cell_candidates"), out[:6]))
+
+
+def trellis_edge_cases():
+    """[(name, sequence)] made for the data paths of the trellis and forward kernels that ordinary DNA almost never takes (kernels.h:
+    trellisItems, loadTileThread, forwardPiece); tests/test_emu_trellis.py asserts from the emulator's counters (EmuTrellis) that they
+    take them.  Found by a search over motifs driven by those counters; every record is 25 kb or shorter.
+    - ag_rich, ac_rich: random purines / random {A, C}: reading frames without a stop codon whose exon candidates read acceptor
+      (laVal, list 0) and reverse donor (lrVal, list 1) values more than LIST_WIN - LIST_AHEAD entries back, from HBM;
+    - gt_cag, ct_tac: 600 donor sites two bases apart, then acceptors (and the same on the reverse strand): the short-intron candidates
+      read ldVal (list 2) and rdVal (list 3) back; needs an intron d of more than twice LIST_WIN - LIST_AHEAD bases;
+    - atg_ggt: 300 start codons in one open frame, then 400 donor sites: initial-exon candidates whose igenic predecessor lies
+      0 .. 2100 bases back, among them pay == vigLo and pay == vigLo + 1 of every block alignment;
+    - cag_many: about 4000 in-frame acceptors for the cells of one donor site: thousands of candidates summed into one forward cell, tiles
+      of 30 000 candidates (beyond ITEM_CAP, beyond the threads of the forward kernel);
+    - cag_N_cag: the same reading frame across a run of 3600 N, which the trellis jumps over: predecessors (list and igenic) older
+      than the jump;
+    - orf12k: one single-exon gene of 12 kb (igenic predecessor 12 kb back);
+    - multi_far: the far blocks between a stretch of low and one of high GC content: a piece with two GC classes under the human model"""
+    rng8 = np.random.default_rng(8)
+    ag = "".join(rng8.choice(list("AG"), size=20000))
+    pre = post = "ACGT" * 500
+    return [
+        ("ag_rich", ag),
+        ("ac_rich", random_dna(20000, 77, "AC")),
+        ("gt_cag", pre + "GT" * 600 + "CAG" * 40 + post),
+        ("ct_tac", pre + "CT" * 600 + "TAC" * 40 + post),
+        ("atg_ggt", pre + "ATG" * 300 + "GGT" * 400 + post),
+        ("cag_many", "ACGT" * 250 + "ATG" + "CAG" * 3990 + "GTAAGT" + post),
+        ("cag_N_cag", pre + "ATG" + "CAG" * 1500 + "N" * 3600 + "CAG" * 1500 + "GTAAGT" + post),
+        ("orf12k", random_dna(1000, 3) + "ATG" + "GCC" * 4000 + "TAA" + random_dna(1000, 4)),
+        ("multi_far", _gc_dna(9000, 0.30, 9101) + "CT" * 600 + "TAC" * 40 + "ACGT" * 200 + "GT" * 600 + "CAG" * 40 + ag[:3000] + _gc_dna(9000, 0.66, 9102)),
+    ]
+
+
+def trellis_edge_long(n=390000):
+    """one record of n bases that AUGX_SEG_LEN=77000 cuts into five segments under the human model (a segment is at least five check
+    windows of maxexonlength long): random DNA with far-predecessor blocks of trellis_edge_cases() across the first and the second cut
+    -- reading frames and their candidates span the seams --, a run of N from before the third cut to beyond the limit of the fix-up
+    that starts there, which therefore gives up (a dead start cannot converge inside a run of N) and is continued by pass 3, and a run
+    of 7000 N across the fourth cut: the fix-up that starts in it and the continuation settle on the truth in the same tiles behind
+    it, and the continuation, which must not stop on the other run's seam, runs over it (found by a search over the length of that run)"""
+    s = random_dna(n, 9500)
+    cuts = [((n + 63) // 64 * k // 5) * 64 for k in range(1, 5)]
+    blocks = dict(trellis_edge_cases())
+    for at, block in ((cuts[0] - 7000, blocks["cag_many"][1000:-2000]), (cuts[1] - 3000, blocks["ag_rich"][:6000]),
+                      (cuts[2] - 9000, "N" * (9000 + n // 5 - 14000)), (cuts[3] - 2000, "N" * 7000)):
+        s = s[:at] + block + s[at + len(block):]
+    assert len(s) == n
+    return s

@@ -64,8 +64,10 @@ def test_emulated_ragged_lengths(species):
 
 
 def adversarial_cases():
-    """dense splice sites (more candidates per tile than the LDS staging holds), 20 kb open reading frames on both strands
-    (exon candidates far outside every LDS window), start-codon repeats, purine / pyrimidine tracts"""
+    """dense splice sites (more candidates per tile than the LDS staging holds), 21 kb open reading frames on both strands (longer
+    than maxexonlength: no exon candidate spans them, nothing of them is read back from HBM), start-codon repeats, purine / pyrimidine
+    tracts (ag_rich: acceptor values read back from HBM).  tests/test_emu_trellis.py asserts these claims from the emulator's counters;
+    the inputs made for every far-window path are helpers.trellis_edge_cases"""
     rng8, rng9 = np.random.default_rng(8), np.random.default_rng(9)
     return {
         "aggt": "AGGT" * 3000,
