@@ -81,6 +81,10 @@ def lib():
                                       ctypes.POINTER(ctypes.c_int64)]
         L.augx_batch_kernel_ms.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_float),
                                            ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
+        _plan = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                 ctypes.POINTER(ctypes.c_int), ctypes.c_void_p]
+        L.augx_plan_segments.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int] + _plan
+        L.augx_batch_plan.argtypes = [ctypes.c_void_p, ctypes.c_void_p] + _plan + [ctypes.c_void_p, ctypes.c_void_p]
         L.augx_batch_forward.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         L.augx_batch_forward_cells.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
         L.augx_batch_destroy.argtypes = [ctypes.c_void_p]
@@ -202,11 +206,13 @@ class Batch:
         for i, s in enumerate(self._keep):
             P[i].seq, P[i].len, P[i].init_kind, P[i].term_kind = s, len(s), iks[i], tks[i]
         self._h = ctypes.c_void_p()
+        self._decoded = False
         _check(L.augx_batch_create(decoder._h, P, self.n, ctypes.byref(self._h)))
         decoder._batches.add(self._h.value)   # (a decoder destroys its live batches before it goes: they hold a pointer to it)
 
     def decode(self, sync=True):
         _check(lib().augx_batch_decode(self.decoder._h, self._h))
+        self._decoded = True
         if sync:
             _check(lib().augx_batch_sync(self.decoder._h))
 
@@ -239,6 +245,14 @@ class Batch:
         decode left it, plane ``plane`` of the arrays that have one per GC class of the piece (fx, plsR)"""
         L = lib()
         return prep_fetch(lambda w, pl, out, cap, nb: L.augx_batch_prep(self.decoder._h, self._h, piece, w, pl, out, cap, nb), which, plane)
+
+    def plan(self):
+        """``augx_batch_plan``: the plan of the trellis passes this batch was created with (see :func:`plan_segments`) and, once it has
+        been decoded, ``seg_stop`` / ``seg_stop2``: where the fix-up of every segment and its continuation stopped (None before)"""
+        L = lib()
+        if not self._decoded:
+            return _plan_query(lambda *a: L.augx_batch_plan(self.decoder._h, self._h, *a, None, None))
+        return _plan_query(lambda *a: L.augx_batch_plan(self.decoder._h, self._h, *a), stops=True)
 
     def forward(self):
         """run the forward algorithm on the decoded batch (``augx_batch_forward``)"""
@@ -379,6 +393,35 @@ def find_cuts(model, seqs, decode_fn, scout=-1):
 
 def device_count():
     return lib().augx_device_count()
+
+
+def _plan_query(call, stops=False):
+    import numpy as np
+    ns, nr, ck = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    est = np.zeros(2, dtype=np.int64)
+    _check(call(None, 0, ctypes.byref(ns), None, 0, ctypes.byref(nr), ctypes.byref(ck), est.ctypes.data_as(ctypes.c_void_p), *((None, None) if stops else ())))
+    segs = np.zeros((ns.value, 5), dtype=np.int32)
+    runs = np.zeros(nr.value + 1, dtype=np.int32)
+    more = ()
+    if stops:
+        more = (np.full(ns.value, -1, dtype=np.int32), np.full(ns.value, -1, dtype=np.int32))
+    _check(call(segs.ctypes.data_as(ctypes.c_void_p), ns.value, ctypes.byref(ns), runs.ctypes.data_as(ctypes.c_void_p), nr.value, ctypes.byref(nr),
+                ctypes.byref(ck), est.ctypes.data_as(ctypes.c_void_p), *[None if a is None else a.ctypes.data_as(ctypes.c_void_p) for a in more]))
+    res = {"segs": segs, "run_seg0": runs[:nr.value + 1] if nr.value else runs[:0], "n_runs": nr.value, "check_tiles": ck.value,
+           "est_tiles": int(est[0]), "est_per_piece": int(est[1])}
+    res["seg_stop"], res["seg_stop2"] = more if stops else (None, None)
+    return res
+
+
+def plan_segments(model, lens, slots):
+    """``augx_plan_segments`` (host only): the plan of the trellis passes for pieces of these lengths on ``slots`` workgroups.
+    ``segs``: one row (piece, k, t0, t1, tlim) per segment, in tiles of 64 bases; ``run_seg0``: run r of pass 1 is the segments
+    run_seg0[r] .. run_seg0[r + 1] - 1 (empty: one workgroup per segment); ``est_tiles`` / ``est_per_piece``: the estimate the plan was
+    chosen by and that of the best plan that cuts every piece on its own"""
+    import numpy as np
+    a = np.ascontiguousarray(lens, dtype=np.int64)
+    L = lib()
+    return _plan_query(lambda *args: L.augx_plan_segments(model.tables_ptr, a.ctypes.data_as(ctypes.c_void_p), len(a), slots, *args))
 
 
 def partition_lpt(lens, n_bins):

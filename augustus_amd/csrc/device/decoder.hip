@@ -926,10 +926,12 @@ int augx_batch_create(augx_decoder *d, const augx_piece *pieces, int n, augx_bat
     keep(V.pathRec, Z.pathCap * 3);
     // segments of the trellis: enough workgroups for every compute unit, none shorter than what a fix-up needs
     b->plan = planSegments(L, d->model->m.t, d->nCU / d->share > 0 ? d->nCU / d->share : 1, d->dense ? -1 : 0); // (dense kernels: one workgroup per piece)
-    SegDesc *dSegs = nullptr; int32_t *dSeg0 = nullptr;
-    const int nSegs = (int)b->plan.segs.size();
+    SegDesc *dSegs = nullptr; int32_t *dSeg0 = nullptr, *dRun0 = nullptr;
+    const int nSegs = (int)b->plan.segs.size(), nRuns = b->plan.nRuns();
     keep(dSegs, nSegs); keep(dSeg0, n + 1);
+    if (nRuns > 0) keep(dRun0, nRuns + 1);
     V.nSegs = nSegs; V.segs = dSegs; V.pieceSeg0 = dSeg0; V.segCheckTiles = b->plan.checkTiles;
+    V.nRuns = nRuns; V.runSeg0 = dRun0;
     if (const char *e = getenv("AUGX_SEG_CHECK_TILES")) V.segCheckTiles = atoi(e); // (tests of the give-up path: an unreachable check length)
     keep(V.segStop, nSegs); keep(V.segStatus, nSegs); keep(V.segD, nSegs); keep(V.brkPos, nSegs); keep(V.brkOff, nSegs);
     keep(V.segStop2, nSegs); keep(V.segD2, nSegs); keep(V.pieceCovered, n);
@@ -947,6 +949,7 @@ int augx_batch_create(augx_decoder *d, const augx_piece *pieces, int n, augx_bat
     HIP_TRY(hipMemcpy(dCp, L.chunkPiece.data(), sizeof(int32_t) * L.nChunks, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(dSegs, b->plan.segs.data(), sizeof(SegDesc) * nSegs, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(dSeg0, b->plan.pieceSeg0.data(), sizeof(int32_t) * (n + 1), hipMemcpyHostToDevice));
+    if (nRuns > 0) HIP_TRY(hipMemcpy(dRun0, b->plan.runSeg0.data(), sizeof(int32_t) * (nRuns + 1), hipMemcpyHostToDevice));
     HIP_TRY(hipMemset(dRaw, 'n', (size_t)Z.N));
     HIP_TRY(hipMemset(V.gcPlane, 0, (size_t)Z.N));
     for (int p = 0; p < n; p++)
@@ -1148,7 +1151,9 @@ int augx_batch_decode(augx_decoder *d, augx_batch *b) {
     }
     HIP_TRY(hipMemsetAsync(V.segStatus, 0, sizeof(int32_t) * V.nSegs, st));
 #define AUGX_LAUNCH_TRELLIS(MODE_, grid_) launchTrellis(d->blk, MODE_, V.nearTie, (unsigned)(grid_), st, d->dT, b->dV) // (near ties counted: the build whose chain wavefront flags them)
-    AUGX_LAUNCH_TRELLIS(0, V.nSegs);                 // pass 1: every segment at once (one workgroup per piece when no piece is cut)
+    // pass 1: every segment at once (one workgroup per piece when no piece is cut), or one workgroup per run of segments
+    if (V.nRuns > 0) AUGX_LAUNCH_TRELLIS(TRELLIS_RUNS, V.nRuns);
+    else AUGX_LAUNCH_TRELLIS(0, V.nSegs);
     if (b->plan.cut()) {
         HIP_TRY(hipMemsetAsync(V.segStop2, 0xFF, sizeof(int32_t) * V.nSegs, st));
         HIP_TRY(hipMemsetAsync(V.pieceCovered, 0xFF, sizeof(int32_t) * n, st));
@@ -1198,6 +1203,76 @@ int augx_batch_decode(augx_decoder *d, augx_batch *b) {
         }
     }
     HIP_TRY(hipEventRecord(b->ev[3], st));
+    if (timingFirst && !d->dense) { // (developer aid: the plan of the trellis passes and what became of its fix-ups)
+        const SegPlan &P = b->plan;
+        int longestSeg = 0, longestRun = 0, gaveUp = 0;
+        for (const SegDesc &sd : P.segs) if (sd.t1 - sd.t0 > longestSeg) longestSeg = sd.t1 - sd.t0;
+        for (int r = 0; r < P.nRuns(); r++) {
+            int len = 0;
+            for (int q = P.runSeg0[r]; q < P.runSeg0[r + 1]; q++) len += P.segs[q].t1 - P.segs[q].t0;
+            if (len > longestRun) longestRun = len;
+        }
+        if (P.cut()) {
+            std::vector<int32_t> stop(P.segs.size());
+            HIP_TRY(hipStreamSynchronize(st));
+            HIP_TRY(hipMemcpy(stop.data(), V.segStop, sizeof(int32_t) * stop.size(), hipMemcpyDeviceToHost));
+            for (size_t q = 0; q < stop.size(); q++) gaveUp += P.segs[q].k > 0 && stop[q] <= -2;
+        }
+        fprintf(stderr, "augx timing:       trellis plan: %d segments of %d pieces, %d runs, longest run %d tiles, longest segment %d tiles, estimate %lld tiles (pieces cut one by one: %lld); %d fix-ups gave up\n",
+                (int)P.segs.size(), n, P.nRuns(), longestRun, longestSeg, (long long)P.estTiles, (long long)P.estPerPiece, gaveUp);
+    }
+    return AUGX_OK;
+}
+
+namespace {
+// the plan as the flat arrays of augx_plan_segments / augx_batch_plan
+int planOut(const SegPlan &P, int32_t *segs, int cap_segs, int *n_segs, int32_t *run_seg0, int cap_runs, int *n_runs, int *check_tiles, int64_t *est) {
+    const int nS = (int)P.segs.size(), nR = P.nRuns();
+    if (n_segs) *n_segs = nS;
+    if (n_runs) *n_runs = nR;
+    if (check_tiles) *check_tiles = P.checkTiles;
+    if (est) { est[0] = P.estTiles; est[1] = P.estPerPiece; }
+    if ((segs && cap_segs < nS) || (run_seg0 && cap_runs < nR)) { setLastError("augx plan query: output arrays too small"); return AUGX_E_ARG; }
+    if (segs)
+        for (int q = 0; q < nS; q++) {
+            const SegDesc &sd = P.segs[q];
+            int32_t *o = segs + (size_t)q * 5;
+            o[0] = sd.piece; o[1] = sd.k; o[2] = sd.t0; o[3] = sd.t1; o[4] = sd.tlim;
+        }
+    if (run_seg0)
+        for (int r = 0; r <= nR && nR > 0; r++) run_seg0[r] = P.runSeg0[r];
+    return AUGX_OK;
+}
+} // namespace
+
+int augx_plan_segments(const augx_tables *t, const int64_t *lens, int n, int slots, int32_t *segs, int cap_segs, int *n_segs,
+                       int32_t *run_seg0, int cap_runs, int *n_runs, int *check_tiles, int64_t *est) {
+    if (!t || !lens || n < 1 || slots < 1) { setLastError("augx_plan_segments: bad argument"); return AUGX_E_ARG; }
+    try {
+        std::vector<augx_piece> pieces((size_t)n);
+        for (int p = 0; p < n; p++) { pieces[p].seq = nullptr; pieces[p].len = lens[p]; pieces[p].init_kind = 0; pieces[p].term_kind = 0; }
+        BatchLayout L;
+        L.build(pieces.data(), n);
+        return planOut(planSegments(L, *t, slots, modelIsDense(*t) ? -1 : 0), segs, cap_segs, n_segs, run_seg0, cap_runs, n_runs, check_tiles, est);
+    } catch (const std::exception &e) { setLastError(std::string("augx_plan_segments: ") + e.what()); return AUGX_E_ARG; }
+}
+
+int augx_batch_plan(augx_decoder *d, augx_batch *b, int32_t *segs, int cap_segs, int *n_segs, int32_t *run_seg0, int cap_runs, int *n_runs,
+                    int *check_tiles, int64_t *est, int32_t *seg_stop, int32_t *seg_stop2) {
+    if (!d || !b) { setLastError("augx_batch_plan: NULL argument"); return AUGX_E_ARG; }
+    const int rc = planOut(b->plan, segs, cap_segs, n_segs, run_seg0, cap_runs, n_runs, check_tiles, est);
+    if (rc || (!seg_stop && !seg_stop2)) return rc;
+    const size_t nS = b->plan.segs.size();
+    if (cap_segs < (int)nS) { setLastError("augx_batch_plan: output arrays too small"); return AUGX_E_ARG; }
+    if (!b->decoded) { setLastError("augx_batch_plan: the batch has not been decoded"); return AUGX_E_ARG; }
+    if (!b->plan.cut()) { // (no fix-ups: nothing was written)
+        for (size_t q = 0; q < nS; q++) { if (seg_stop) seg_stop[q] = -1; if (seg_stop2) seg_stop2[q] = -1; }
+        return AUGX_OK;
+    }
+    HIP_TRY(hipSetDevice(d->device));
+    HIP_TRY(hipStreamSynchronize(d->stream));
+    if (seg_stop) HIP_TRY(hipMemcpy(seg_stop, b->V.segStop, sizeof(int32_t) * nS, hipMemcpyDeviceToHost));
+    if (seg_stop2) HIP_TRY(hipMemcpy(seg_stop2, b->V.segStop2, sizeof(int32_t) * nS, hipMemcpyDeviceToHost));
     return AUGX_OK;
 }
 

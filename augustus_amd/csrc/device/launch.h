@@ -7,6 +7,7 @@
 
 namespace augx { namespace dev {
 // kTrellis<BLK, MODE, TIES> (k_trellis.hip; kernels.h: trellisPiece)
+constexpr int TRELLIS_RUNS = 4; // `mode` of launchTrellis: pass 1 (MODE 0) with one workgroup per run of segments (BatchView::runSeg0)
 void launchTrellis(int blk, int mode, bool ties, unsigned grid, hipStream_t st, const DevTables *T, const BatchView *B);
 // kCand<BLK, MULTI, DENSE> (k_cand.hip; kernels.h: candWorkgroup)
 void launchCand(int blk, bool multi, bool dense, unsigned grid, hipStream_t st, const DevTables *T, const BatchView &W);

@@ -105,8 +105,14 @@ constexpr int SEG_CONT_ROUNDS = 3; // launches of pass 3 (one continuation per p
 struct SegPlan {
     std::vector<SegDesc> segs;
     std::vector<int32_t> pieceSeg0;
+    // runs of pass 1: run r is the segments [runSeg0[r], runSeg0[r+1]), done one after the other by one workgroup -- the tail of a
+    // piece, whole pieces, the head of the next one; never two segments of one piece.  Empty: one workgroup per segment
+    std::vector<int32_t> runSeg0;
     int checkTiles = 0;
+    int64_t estTiles = 0;       // estimated time of the trellis passes of this plan, in tiles of one workgroup (0: the plan was not chosen by estimate)
+    int64_t estPerPiece = 0;    // ... of the best plan that cuts every piece on its own (or does not cut)
     bool cut() const { return segs.size() + 1 > pieceSeg0.size(); } // some piece has more than one segment
+    int nRuns() const { return runSeg0.empty() ? 0 : (int)runSeg0.size() - 1; }
 };
 inline int segCheckTiles(const augx_tables &t) {
     int reach = t.max_exon_len > t.d ? t.max_exon_len : t.d;
@@ -119,6 +125,79 @@ inline bool segmentsSupported(const augx_tables &t) {
     const int dL = t.d - 2 - t.De - t.As - 2 - t.U;
     return t.state_kind[t.synch_state] == AUGX_K_IGENIC && dL >= 4 * WAVE && t.reachable[t.synch_state];
 }
+// Estimated length of pass 2 in tiles: `nFix` fix-ups on `slots` workgroups.  A round of concurrent fix-ups takes as long as its
+// longest one, and the length of a fix-up on random DNA has a heavy tail (CPU emulator, 176 fix-ups under the human model: mean
+// 374 tiles, median 348, p90 665, longest 1 122): the longest of n grows by about SEG_FIX_PER_BIT tiles per doubling of n.  A second
+// round adds SEG_FIX_ROUND (the fix-ups of the second round start when those of the first end, so it ends with a long one that
+// started late).  Sources, profiles/EXPERIMENTS.md "runs of segments": that CPU distribution for one round, and for two rounds
+// the device's pass 2 of the bench shape cut piece by piece (412 fix-ups on 256 compute units, human model): 27.7 ms = 1 770 tiles
+// at 4.1 M positions/s.  The device's time of ONE round has not been measured yet; refit when it is.
+constexpr int64_t SEG_FIX_MEAN = 374, SEG_FIX_PER_BIT = 100, SEG_FIX_ROUND = 570;
+inline int64_t segFixTiles(int64_t nFix, int slots) {
+    if (nFix <= 0) return 0;
+    const int64_t rounds = (nFix + slots - 1) / slots, first = nFix < slots ? nFix : slots;
+    int bits = 0;
+    while ((first >> bits) > 0) bits++;
+    return SEG_FIX_MEAN + SEG_FIX_PER_BIT * bits + (rounds - 1) * SEG_FIX_ROUND;
+}
+// A plan over the whole device: the concatenated tiles of the batch cut into at most `slots` runs whose longest is as short as
+// the rules for a cut allow (binary search on the longest run; for a given bound every run takes the furthest legal cut).  A cut
+// is legal between two pieces, or inside a piece where every segment it makes is at least minSeg tiles -- but for the first
+// segment of a piece, which has no fix-up of its own and only has to hold the look-back of the next one: headMin tiles.
+// Returns the longest run (0: no plan), the cuts inside pieces as (piece, tile) and the first piece-or-cut of every run.
+struct RunCuts {
+    std::vector<std::pair<int, int>> cuts;      // (piece, first tile of the segment that starts there), ascending
+    std::vector<std::pair<int, int>> runStart;  // (piece, tile) where every run begins
+    int64_t longest = 0;
+};
+inline bool cutRunsWithin(const std::vector<int> &tiles, int64_t B, int slots, int minSeg, int headMin, RunCuts *out) {
+    const int n = (int)tiles.size();
+    // the smallest remainder >= rmin of a piece that segments of minSeg .. B tiles can tile (the last one may be shorter than B: the
+    // run goes on into the next piece), -1: none -- m segments tile every remainder in [m * minSeg, m * B]
+    auto tileable = [&](int64_t rmin) -> int64_t {
+        if (B < minSeg) return -1;
+        if (rmin < minSeg) rmin = minSeg;
+        const int64_t m = (rmin + B - 1) / B;
+        return m * minSeg <= rmin ? rmin : m * minSeg;
+    };
+    if (out) { out->cuts.clear(); out->runStart.clear(); out->longest = 0; }
+    int p = 0, c = 0, runs = 0; // the next run starts at tile c of piece p
+    while (p < n) {
+        if (++runs > slots) return false;
+        if (out) out->runStart.push_back({p, c});
+        int64_t used = 0;
+        const int64_t rem = tiles[p] - c;
+        if (rem > B) { // the run ends inside the piece it starts in
+            const int64_t r = tileable(rem - B), low = c == 0 ? headMin : minSeg;
+            if (r < 0 || rem - r < low) return false;
+            c = (int)(tiles[p] - r); used = rem - r;
+            if (out) out->cuts.push_back({p, c});
+        } else { // the rest of the piece, whole pieces while they fit, the head of the next one if a legal cut is in reach
+            used = rem; p++; c = 0;
+            while (p < n && used + tiles[p] <= B) used += tiles[p++];
+            if (p < n) {
+                const int64_t r = tileable(tiles[p] - (B - used));
+                if (r >= 0 && tiles[p] - r >= headMin) {
+                    c = (int)(tiles[p] - r); used += c;
+                    if (out) out->cuts.push_back({p, c});
+                }
+            }
+        }
+        if (out && used > out->longest) out->longest = used;
+    }
+    return true;
+}
+inline bool planRuns(const std::vector<int> &tiles, int slots, int minSeg, int headMin, RunCuts &R) {
+    int64_t total = 0;
+    for (int t : tiles) total += t;
+    if (total <= 0 || slots < 1) return false;
+    int64_t lo = (total + slots - 1) / slots - 1, hi = total; // lo: too short for `slots` runs; hi: one run holds the batch
+    while (hi - lo > 1) {
+        const int64_t mid = lo + (hi - lo) / 2;
+        if (cutRunsWithin(tiles, mid, slots, minSeg, headMin, nullptr)) hi = mid; else lo = mid;
+    }
+    return cutRunsWithin(tiles, hi, slots, minSeg, headMin, &R);
+}
 // segTiles: tiles per segment wanted (0: choose so that `slots` workgroups are busy; < 0: never cut).  AUGX_SEG_LEN (bases)
 // overrides it (tests; 0 = never cut).
 inline SegPlan planSegments(const BatchLayout &L, const augx_tables &t, int slots, int segTiles = 0) {
@@ -127,6 +206,9 @@ inline SegPlan planSegments(const BatchLayout &L, const augx_tables &t, int slot
     const int n = L.nPieces;
     if (const char *e = getenv("AUGX_SEG_LEN")) { const long v = atol(e); segTiles = v <= 0 ? -1 : (int)((v + WAVE - 1) / WAVE); }
     const int minSeg = 5 * P.checkTiles; // a segment holds its own fix-up (convergence + checkTiles) and the look-back of the next one
+    // the first segment of a piece has no fix-up: it holds the look-back of the next one only (what fix-up 1 reads of it are the true
+    // values, and no fix-up writes there).  Only the plan over the whole device makes such heads
+    const int headMin = P.checkTiles + 2;
     std::vector<int> tiles(n);
     int64_t total = 0;
     int maxTiles = 0;
@@ -137,10 +219,12 @@ inline SegPlan planSegments(const BatchLayout &L, const augx_tables &t, int slot
         while (k > 1 && tiles[p] / k < minSeg) k--;
         return k < 1 ? 1 : k;
     };
+    RunCuts R;
+    bool useRuns = false;
     if (segTiles == 0) {
-        // estimate of the time of the three passes for a candidate segment length: rounds of `slots` concurrent workgroups,
-        // each as long as the longest segment / a typical fix-up (convergence within ~400 tiles on random DNA, then the check)
-        const int64_t fixLen = 450; // (convergence ~400 tiles on random DNA + the check window, which follows the candidates that really cross the stop point)
+        // estimate of the time of the three passes for a candidate plan, in tiles.  Pieces cut one by one: rounds of `slots`
+        // concurrent workgroups (the hardware hands out the segments as compute units fall free), each as long as the longest
+        // segment; then the fix-ups (segFixTiles)
         int64_t bestCost = -1;
         int best = -1;
         for (int k = 1; k <= 64; k++) {
@@ -153,12 +237,46 @@ inline SegPlan planSegments(const BatchLayout &L, const augx_tables &t, int slot
                 const int64_t len = (tiles[p] + kp - 1) / kp;
                 if (len > longest) longest = len;
             }
-            int64_t cost = (nSeg + slots - 1) / slots * longest + (nFix + slots - 1) / slots * fixLen;
+            int64_t cost = (nSeg + slots - 1) / slots * longest + segFixTiles(nFix, slots);
             // (the fix-ups are extra work and their length has a heavy tail: cutting must promise a clear gain to be chosen)
-            if (k > 1) cost += cost / 6;
-            if (bestCost < 0 || cost < bestCost) { bestCost = cost; best = k == 1 ? -1 : st; }
+            if (nFix > 0) cost += cost / 6;
+            if (bestCost < 0 || cost < bestCost) { bestCost = cost; best = nFix == 0 ? -1 : st; }
         }
         segTiles = best;
+        P.estPerPiece = P.estTiles = bestCost;
+        // runs over the whole device: one workgroup per run, all at once; as long as the longest run, and one round of fix-ups
+        if (n > 0 && planRuns(tiles, slots, minSeg, headMin, R) && !R.cuts.empty()) {
+            int64_t cost = R.longest + segFixTiles((int64_t)R.cuts.size(), slots);
+            cost += cost / 6;
+            if (cost < bestCost) { useRuns = true; P.estTiles = cost; }
+        }
+    }
+    P.pieceSeg0.assign((size_t)n + 1, 0);
+    auto addSeg = [&](int p, int k, int t0, int t1) {
+        SegDesc d;
+        d.piece = p; d.k = k; d.t0 = t0; d.t1 = t1;
+        d.tlim = d.t1 - P.checkTiles - 2;
+        d.pad = 0;
+        P.segs.push_back(d);
+    };
+    if (useRuns) {
+        size_t ci = 0, ri = 0;
+        for (int p = 0; p < n; p++) {
+            P.pieceSeg0[p] = (int32_t)P.segs.size();
+            int k = 0, t0 = 0;
+            for (;; k++) {
+                // (a run begins with this segment: at the first tile of a piece or at a cut)
+                if (ri < R.runStart.size() && R.runStart[ri].first == p && R.runStart[ri].second == t0) { P.runSeg0.push_back((int32_t)P.segs.size()); ri++; }
+                const bool more = ci < R.cuts.size() && R.cuts[ci].first == p;
+                const int t1 = more ? R.cuts[ci].second : tiles[p];
+                addSeg(p, k, t0, t1);
+                if (!more) break;
+                t0 = t1; ci++;
+            }
+        }
+        P.pieceSeg0[n] = (int32_t)P.segs.size();
+        P.runSeg0.push_back((int32_t)P.segs.size());
+        return P;
     }
     if (segTiles > 0 && segTiles < minSeg) segTiles = minSeg;
     std::vector<int> kOf(n, 1);
@@ -172,19 +290,11 @@ inline SegPlan planSegments(const BatchLayout &L, const augx_tables &t, int slot
             for (int p = 0; p < n && extra > 0; p++)
                 if (kOf[p] > 1 && tiles[p] / (kOf[p] + 1) >= minSeg) { kOf[p]++; extra--; }
     }
-    P.pieceSeg0.assign((size_t)n + 1, 0);
     for (int p = 0; p < n; p++) {
         const int kp = kOf[p];
         P.pieceSeg0[p] = (int32_t)P.segs.size();
-        for (int k = 0; k < kp; k++) {
-            SegDesc d;
-            d.piece = p; d.k = k;
-            d.t0 = (int32_t)((int64_t)tiles[p] * k / kp);
-            d.t1 = (int32_t)((int64_t)tiles[p] * (k + 1) / kp);
-            d.tlim = d.t1 - P.checkTiles - 2;
-            d.pad = 0;
-            P.segs.push_back(d);
-        }
+        for (int k = 0; k < kp; k++)
+            addSeg(p, k, (int32_t)((int64_t)tiles[p] * k / kp), (int32_t)((int64_t)tiles[p] * (k + 1) / kp));
     }
     P.pieceSeg0[n] = (int32_t)P.segs.size();
     return P;

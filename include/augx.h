@@ -307,6 +307,18 @@ int augx_batch_decode(augx_decoder *d, augx_batch *b);            /* all kernels
 int augx_batch_sync(augx_decoder *d);
 int augx_batch_paths(augx_decoder *d, augx_batch *b, augx_path *out /* array[n] */);      /* D2H + unpack */
 int augx_batch_kernel_ms(augx_decoder *d, augx_batch *b, float *prep_ms, float *trellis_ms, float *back_ms);
+/* read-only query of the plan of the trellis passes (host only, no device needed): the segments a batch of pieces of these lengths
+ * is decoded in on `slots` workgroups -- 5 int32 each: piece, index in the piece, first tile, end tile (tiles of 64 bases), last tile
+ * its fix-up may rewrite -- and the runs of pass 1: run r is the segments run_seg0[r] .. run_seg0[r + 1] - 1, done one after the other
+ * by one workgroup (*n_runs = 0: one workgroup per segment).  est[0]: the estimate the plan was chosen by, est[1]: that of the best
+ * plan that cuts every piece on its own, both in tiles (0: not chosen by estimate).  Any output may be NULL; AUGX_E_ARG when an
+ * array is too small (*n_segs and *n_runs are set).  augx_batch_plan: the same for the plan a batch was created with, and, after a
+ * decode, where the fix-up of every segment stopped (seg_stop: the last tile rewritten, <= -2: gave up; seg_stop2: where its
+ * continuation stopped, -1: none; the entries of a piece's first segment, which has no fix-up, mean nothing; all -1 when no piece is cut) */
+int augx_plan_segments(const augx_tables *t, const int64_t *lens, int n, int slots, int32_t *segs /* [cap_segs][5] */, int cap_segs, int *n_segs,
+                       int32_t *run_seg0 /* [cap_runs + 1] */, int cap_runs, int *n_runs, int *check_tiles, int64_t *est /* [2] */);
+int augx_batch_plan(augx_decoder *d, augx_batch *b, int32_t *segs, int cap_segs, int *n_segs, int32_t *run_seg0, int cap_runs, int *n_runs,
+                    int *check_tiles, int64_t *est, int32_t *seg_stop /* [cap_segs] */, int32_t *seg_stop2 /* [cap_segs] */);
 /* test hook: copy the dense ln V[j][s] matrix (len*S doubles, -inf = absent) of piece i to host; only
  * valid on a decoder created with AUGX_DEBUG_CELLS=1 in the environment */
 int augx_batch_cells(augx_decoder *d, augx_batch *b, int piece, double *out);
