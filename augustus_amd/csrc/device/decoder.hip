@@ -271,22 +271,27 @@ __global__ void __launch_bounds__(SCAN_T) kSiteScanApply(const DevTables *__rest
 #pragma unroll
     for (int f = 0; f < 6; f++) B.nsm[fidx(g, f, 6)] = (uint32_t)v[NCNT + f];
 }
-__global__ void __launch_bounds__(SCAN_T) kFxScanTotals(const DevTables *__restrict__ T, BatchView B, uint64_t *tot /* [nPl][N / SCAN_T][NFX] */) { // grid.y = plane
+// the content tables in fixed point, one record per pattern (kernels.h: FxTabs): made once, when the decoder uploads its model
+__global__ void __launch_bounds__(256) kFxTabs(const DevTables *__restrict__ T, uint64_t *out, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = fxTabEntry(*T, i);
+}
+__global__ void __launch_bounds__(SCAN_T) kFxScanTotals(const DevTables *__restrict__ T, FxTabs X, BatchView B, uint64_t *tot /* [nPl][N / SCAN_T][NFX] */) { // grid.y = plane
     __shared__ ScanLds<NFX> L;
     __shared__ SlotCodes C;
     C.load(B);
     const int64_t g = (int64_t)blockIdx.x * SCAN_T + threadIdx.x;
     uint64_t v[NFX];
-    if (!k1FxTermsCalc(*T, B, g, blockIdx.y, v, C.c, C.lo, C.lo + 256 + 2 * SLOT_HALO)) return; // (uniform over the block: it belongs to one piece)
+    if (!k1FxTermsRec(*T, X, B, g, blockIdx.y, v, C.c, C.lo, C.lo + 256 + 2 * SLOT_HALO)) return; // (uniform over the block: it belongs to one piece)
     blockTotals<NFX>(v, NFX, L, tot + ((int64_t)blockIdx.y * (B.N / SCAN_T) + blockIdx.x) * NFX);
 }
-__global__ void __launch_bounds__(SCAN_T) kFxScanApply(const DevTables *__restrict__ T, BatchView B, const uint64_t *tot) { // grid.y = plane
+__global__ void __launch_bounds__(SCAN_T) kFxScanApply(const DevTables *__restrict__ T, FxTabs X, BatchView B, const uint64_t *tot) { // grid.y = plane
     __shared__ ScanLds<NFX> L;
     __shared__ SlotCodes C;
     C.load(B);
     const int64_t g = (int64_t)blockIdx.x * SCAN_T + threadIdx.x;
     uint64_t v[NFX];
-    if (!k1FxTermsCalc(*T, B, g, blockIdx.y, v, C.c, C.lo, C.lo + 256 + 2 * SLOT_HALO)) return;
+    if (!k1FxTermsRec(*T, X, B, g, blockIdx.y, v, C.c, C.lo, C.lo + 256 + 2 * SLOT_HALO)) return;
     blockScan<NFX>(v, NFX, L, tot + ((int64_t)blockIdx.y * (B.N / SCAN_T) + blockIdx.x) * NFX);
     uint64_t *fx = B.fx + (int64_t)blockIdx.y * B.N * NFX;
 #pragma unroll
@@ -461,6 +466,7 @@ struct augx_decoder {
     DevTables hostT;          // scalars + DEVICE table pointers
     DevTables *dT = nullptr;
     std::vector<void *> tableBufs;
+    FxTabs fxTabs{};          // the content tables as the prefix scans read them (kernels.h; its buffer is one of tableBufs)
     bool debugCells = false;
     int blk = 8;              // block size of the candidate / trellis kernels for this model (layout.h: chooseBlockSize)
     int nCU = 256;            // compute units of the device = trellis workgroups in flight (one per CU: 155 KB of LDS each)
@@ -724,6 +730,18 @@ int augx_decoder_create(const augx_model *m, int device, augx_decoder **out) {
         }
         HIP_TRY(hipMalloc((void **)&d->dT, sizeof(DevTables)));
         HIP_TRY(hipMemcpy(d->dT, &d->hostT, sizeof(DevTables), hipMemcpyHostToDevice));
+        {   // the fixed-point records of the content scans, converted by the device from the tables it has just been given
+            const int64_t nEx = (int64_t)d->hostT.C * d->hostT.NP * FXREC, nIn = (int64_t)d->hostT.C * d->hostT.NPin, nAll = nEx + 2 * nIn + 3;
+            uint64_t *p = nullptr, tail[3];
+            HIP_TRY(hipMalloc((void **)&p, (size_t)nAll * sizeof(uint64_t)));
+            d->tableBufs.push_back(p);
+            hipLaunchKernelGGL(kFxTabs, dim3((unsigned)((nAll + 255) / 256)), dim3(256), 0, d->stream, d->dT, p, nAll);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(tail, p + nEx + 2 * nIn, sizeof(tail), hipMemcpyDeviceToHost, d->stream));
+            HIP_TRY(hipStreamSynchronize(d->stream));
+            d->fxTabs.ex = p; d->fxTabs.in = p + nEx;
+            d->fxTabs.nCoding = tail[0]; d->fxTabs.quarter[0] = tail[1]; d->fxTabs.quarter[1] = tail[2];
+        }
         return AUGX_OK;
     }();
     if (rc) { augx_decoder_destroy(d); return rc; }
@@ -1067,9 +1085,9 @@ int augx_batch_decode(augx_decoder *d, augx_batch *b) {
         b->chunkTotPlanes = V.nPl;
     }
     if (d->dense && !b->utrScanned) utrScan();
-    hipLaunchKernelGGL(kFxScanTotals, dim3(nScan, V.nPl), dim3(SCAN_T), 0, st, d->dT, V, V.chunkTot);
+    hipLaunchKernelGGL(kFxScanTotals, dim3(nScan, V.nPl), dim3(SCAN_T), 0, st, d->dT, d->fxTabs, V, V.chunkTot);
     hipLaunchKernelGGL(kChunkOffsets, dim3(n, V.nPl, NFX), dim3(64), 0, st, V.chunkTot, V, NFX, NFX);
-    hipLaunchKernelGGL(kFxScanApply, dim3(nScan, V.nPl), dim3(SCAN_T), 0, st, d->dT, V, V.chunkTot);
+    hipLaunchKernelGGL(kFxScanApply, dim3(nScan, V.nPl), dim3(SCAN_T), 0, st, d->dT, d->fxTabs, V, V.chunkTot);
     hipLaunchKernelGGL(kSignals, dim3(gridN), dim3(256), 0, st, d->dT, V);
     hipLaunchKernelGGL(kSiteSignals, dim3((unsigned)((V.listCap + 255) / 256), 4), dim3(256), 0, st, d->dT, V);
     hipLaunchKernelGGL(kSiteConsts, dim3(gridN, V.nPl), dim3(256), 0, st, d->dT, V);

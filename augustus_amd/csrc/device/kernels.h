@@ -310,6 +310,76 @@ AUGX_HD void k1FxTerms(const DevTables &T, const BatchView &B, int64_t g, int pl
     for (int i = 0; i < NFX; i++) fx[fidx(g, i, NFX)] = out[i];
 }
 
+// ---- the content tables as the prefix scans read them: one record per (class, exon pattern) with the nine fixed-point terms
+// toFx(tab[tb][frame][pattern]), tb-major (72 bytes: the forward terms of a base are one record, the reverse terms another -- with
+// the tables as they are the 18 look-ups of a base land in 18 cache lines, and every term is converted from double in both scan
+// passes of every decode although the tables never change while a decoder lives), and the intron table in fixed point, without and
+// with the soft-masking bonus (the bonus is added BEFORE the conversion, as k1FxTermsCalc does).  Built once per decoder by the
+// device itself (decoder.hip: kFxTabs) with the same toFx, so that every entry -- a non-finite one included -- has the bits the
+// conversion per base gave.
+constexpr int FXREC = 9;
+struct FxTabs {
+    const uint64_t *ex;    // [C][NP][FXREC]: ex_emi, ex_init, ex_et of the three frames
+    const uint64_t *in;    // [2][C][NPin]: in_emi, in_emi + lnSoft
+    uint64_t nCoding;      // toFx(ln_n_coding): a pattern with a base that is no nucleotide
+    uint64_t quarter[2];   // toFx(ln_quarter), toFx(ln_quarter + lnSoft)
+};
+// entry i of the tables of FxTabs (i < C NP FXREC: ex, then in, then nCoding, quarter[0..1]): one conversion
+AUGX_HD uint64_t fxTabEntry(const DevTables &T, int64_t i) {
+    const int64_t nEx = (int64_t)T.C * T.NP * FXREC, nIn = (int64_t)T.C * T.NPin;
+    if (i < nEx) {
+        const int64_t cp = i / FXREC;
+        const int tb = (int)(i % FXREC) / 3, fr = (int)(i % FXREC) % 3, c = (int)(cp / T.NP), pn = (int)(cp % T.NP);
+        const TabPtr tab = tb == 0 ? T.ex_emi : tb == 1 ? T.ex_init : T.ex_et;
+        return toFx(tab[((int64_t)c * 3 + fr) * T.NP + pn]);
+    }
+    i -= nEx;
+    if (i < 2 * nIn) return toFx(T.in_emi[i % nIn] + (i < nIn ? 0.0 : T.lnSoft));
+    i -= 2 * nIn;
+    return i == 0 ? toFx(T.ln_n_coding) : toFx(T.ln_quarter + (i == 1 ? 0.0 : T.lnSoft));
+}
+// k1FxTermsCalc from the records: the same 20 terms, bit for bit
+AUGX_HD bool k1FxTermsRec(const DevTables &T, const FxTabs &X, const BatchView &B, int64_t g, int pl, uint64_t out[NFX],
+                          const uint8_t *lcode = nullptr, int lLo = 0, int lHi = 0) {
+    int p = B.chunkPiece[g / CHUNK];
+    if (pl > 0 && pl >= B.nPlanes[p]) return false; // (this piece has no such plane)
+    int64_t o = B.off[p];
+    int q = (int)(g - o - 1);
+    for (int i = 0; i < NFX; i++) out[i] = 0;
+    Piece P;
+    P.t = &T; P.n = B.len[p]; P.c = B.cls[p] < 0 ? -1 : B.planeCls[p * MAXPL + pl]; P.o = o; P.code = B.code + o + 1; P.fx = nullptr; P.nsm = nullptr; P.sig = nullptr;
+    P.lcode = lcode; P.lLo = lLo; P.lHi = lHi;
+    if (q >= 0 && q < B.len[p] && P.c >= 0) {
+    const int k = T.k, c = P.c;
+    const int pn = q >= k ? P.pat(q - k, k + 1) : -1;
+    const int rn = P.rcpat(q, k + 1);
+    // (all nine terms of a record are loaded -- 72 contiguous bytes -- and the frames picked afterwards: forward strand frame
+    //  (q + a) mod 3, reverse strand frame (a - q) mod 3, reference ExonModel::seqProb, src/exonmodel.cc:1957-1966)
+    const int r = mod3(q);
+    uint64_t f[FXREC], v[FXREC];
+    const uint64_t *fr = X.ex + ((int64_t)c * T.NP + (pn >= 0 ? pn : 0)) * FXREC, *rr = X.ex + ((int64_t)c * T.NP + (rn >= 0 ? rn : 0)) * FXREC;
+    for (int i = 0; i < FXREC; i++) { f[i] = fr[i]; v[i] = rr[i]; }
+    for (int tb = 0; tb < 3; tb++) {
+        const uint64_t f0 = pn >= 0 ? f[tb * 3] : X.nCoding, f1 = pn >= 0 ? f[tb * 3 + 1] : X.nCoding, f2 = pn >= 0 ? f[tb * 3 + 2] : X.nCoding;
+        const uint64_t v0 = rn >= 0 ? v[tb * 3] : X.nCoding, v1 = rn >= 0 ? v[tb * 3 + 1] : X.nCoding, v2 = rn >= 0 ? v[tb * 3 + 2] : X.nCoding;
+        out[(0 * 3 + 0) * 3 + tb] = r == 0 ? f0 : r == 1 ? f1 : f2;
+        out[(0 * 3 + 1) * 3 + tb] = r == 0 ? f1 : r == 1 ? f2 : f0;
+        out[(0 * 3 + 2) * 3 + tb] = r == 0 ? f2 : r == 1 ? f0 : f1;
+        out[(1 * 3 + 0) * 3 + tb] = r == 0 ? v0 : r == 1 ? v2 : v1;
+        out[(1 * 3 + 1) * 3 + tb] = r == 0 ? v1 : r == 1 ? v0 : v2;
+        out[(1 * 3 + 2) * 3 + tb] = r == 0 ? v2 : r == 1 ? v1 : v0;
+    }
+    const int soft = (T.soft && B.raw[g] >= 'a' && B.raw[g] <= 'z') ? 1 : 0;
+    const uint64_t *inE = X.in + ((int64_t)soft * T.C + c) * T.NPin;
+    const int ki = T.kIn; // (the intron model's own order: the exon patterns serve where it is k)
+    const int pni = ki == k ? pn : (q >= ki ? P.pat(q - ki, ki + 1) : -1);
+    out[FX_INF] = pni >= 0 ? inE[pni] : X.quarter[soft];
+    const int rn2 = (q + ki < P.n) ? (ki == k ? rn : P.rcpat(q, ki + 1)) : -1;
+    out[FX_INR] = rn2 >= 0 ? inE[rn2] : X.quarter[soft];
+    }
+    return true;
+}
+
 // per-base signal record + end-gate mask of the variable-length states
 constexpr int NSITE = 4;
 AUGX_HD void k1Signals(const DevTables &T, const BatchView &B, int64_t g, const uint8_t *lcode = nullptr, int lLo = 0, int lHi = 0) {
@@ -3328,6 +3398,7 @@ __device__ inline int waveFirstTrue(const int *flag) {
 }
 #endif
 
+constexpr int BT_ROUND = 2048; // bases of a chain run whose back pointers one round of loads of the back-trace covers (32 per lane)
 AUGX_KFN void backtracePiece(const DevTables &T, const BatchView &B, int p) {
     const int n = B.len[p];
     const int64_t o = B.off[p];
@@ -3355,42 +3426,58 @@ AUGX_KFN void backtracePiece(const DevTables &T, const BatchView &B, int p) {
             int cslot = 0; // chain slot of the state (BatchView::bpChain)
             for (int s2 = 0; s2 < state; s2++)
                 if (T.reachable[s2] && (T.kind[s2] == AUGX_K_IGENIC || T.kind[s2] == AUGX_K_GEOMETRIC || T.kind[s2] == AUGX_K_RGEOMETRIC)) cslot++;
-            for (;;) { // find the first base <= cur whose predecessor is not the state itself: 4 bases per lane, 256 per step
-                LV(int, flag);
+            // find the first base <= cur whose predecessor is not the state itself.  The bytes a run will read are known before it is
+            // walked, so a round has the 8 chain bytes of BT_ROUND bases in flight at once and tests them afterwards: load j of lane l
+            // is the pair of bases cur - 128 j - 2 l - {1, 0} (16 contiguous bytes, 1 KB per load over the wavefront).  With one
+            // round of 256 bases in flight a run cost one trip to HBM per 256 bases (profiles/r07_one_batch_kernel_stats.txt).
+            // A pair that would begin before base 0 reads bases 0 and 1 instead (n >= 2 here): its bases are hits for q < 1 whatever it
+            // holds, and no read leaves the slots of the piece
+            const auto chain8 = gp((const uint64_t *)B.bpChain) + o + 1;
+            for (;;) {
+                LV2(uint64_t, cb, BT_ROUND / WAVE); // [2 j]: base cur - 128 j - 2 l, [2 j + 1]: the base before it
+                LV(int, hd); // distance from cur of the lane's hit nearest to cur (BT_ROUND: none)
                 LV(int, wv);
-                LV(int, hit);
                 FOR_LANES(l) {
-                    LX(flag) = 0; LX(wv) = -1; LX(hit) = 4;
 #pragma unroll
-                    for (int k = 3; k >= 0; k--) { // (descending k: the hit nearest to cur is kept)
-                        const int q = cur - 4 * l - k;
-                        const int raw = q >= 1 ? (int)B.bpChain[(o + 1 + q) * 8 + cslot] : -1;
-                        const int ww = raw < 0 || raw == 0xFF ? raw : (raw & 0x7F); // (bit 7: the decision of that cell was a near tie)
-                        if (q < 1 || ww != selfAi) { LX(flag) = 1; LX(wv) = ww; LX(hit) = k; }
+                    for (int j = 0; j < BT_ROUND / WAVE / 2; j++) {
+                        const int q1 = cur - 2 * WAVE * j - 2 * l - 1;
+                        const auto at = chain8 + (q1 < 0 ? 0 : q1);
+                        cb[2 * j + 1][LI] = at[0]; cb[2 * j][LI] = at[1];
                     }
                 }
-                int first = waveFirstTrue(flag);
-                if (first < WAVE) {
-#ifdef AUGX_EMU
-                    const int hk = hit[first], hw = wv[first];
-#else
-                    const int hk = __shfl(hit[0], first, 64), hw = __shfl(wv[0], first, 64);
-#endif
-                    cur -= 4 * first + hk;
+                FOR_LANES(l) {
+                    LX(hd) = BT_ROUND; LX(wv) = -1;
+#pragma unroll
+                    for (int i = BT_ROUND / WAVE - 1; i >= 0; i--) { // (descending distance: the hit nearest to cur is kept)
+                        const int d = WAVE * (i & ~1) + 2 * l + (i & 1), q = cur - d;
+                        const int raw = (int)(cb[i][LI] >> (8 * cslot)) & 0xFF;
+                        const int ww = raw == 0xFF ? raw : (raw & 0x7F); // (bit 7: the decision of that cell was a near tie)
+                        if (q < 1 || ww != selfAi) { LX(hd) = d; LX(wv) = q < 1 ? -1 : ww; }
+                    }
+                }
+                const int dmin = waveMin(hd, 0);
+                if (B.nearTie) { // the cells of this run whose decision (stay / come in from another state) was a near tie
+                    LV(int, nt);
+                    FOR_LANES(l) {
+                        LX(nt) = 0;
+#pragma unroll
+                        for (int i = 0; i < BT_ROUND / WAVE; i++) {
+                            const int d = WAVE * (i & ~1) + 2 * l + (i & 1), raw = (int)(cb[i][LI] >> (8 * cslot)) & 0xFF;
+                            LX(nt) += (d <= dmin && cur - d >= 1 && raw != 0xFF && (raw & 0x80)) ? 1 : 0;
+                        }
+                    }
+                    waveInclScan(nt, 0);
+                    nearTies += waveRead(nt, 0, WAVE - 1);
+                }
+                if (dmin < BT_ROUND) {
+                    const int hw = waveRead(wv, 0, (dmin % (2 * WAVE)) >> 1);
+                    cur -= dmin;
                     w = cur >= 1 ? (uint16_t)hw : BP_NONE;
                     break;
                 }
-                cur -= 4 * WAVE;
+                cur -= BT_ROUND;
             }
             // bases cur..base are in `state`; base `cur` was entered from another state (or cur < 1: sequence start)
-            if (B.nearTie) { // the cells of this run whose decision (stay / come in from another state) was a near tie
-                const int lo2 = cur < 1 ? 1 : cur;
-                for (int q0 = lo2; q0 <= base; q0 += WAVE) {
-                    LV(int, fl);
-                    FOR_LANES(l) { const int q = q0 + l; LX(fl) = (q <= base && B.bpChain[(o + 1 + q) * 8 + cslot] != 0xFF && (B.bpChain[(o + 1 + q) * 8 + cslot] & 0x80)) ? 1 : 0; }
-                    nearTies += waveCount(fl);
-                }
-            }
             if (cur < 1) { eop = 0; ai = -1; }
             else { eop = cur - 1; ai = w; }
         } else if ((kind >= AUGX_K_SINGLE && kind <= AUGX_K_RTERMINAL) || kind == AUGX_K_LESSD || kind == AUGX_K_RLESSD) {
