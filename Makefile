@@ -42,19 +42,20 @@ augustus_amd/libaugx.so: $(HOSTOBJS) $(OBJ)/decoder.o $(KOBJS)
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $^
 
 # TEST INFRASTRUCTURE, built with the product because it needs the product's objects and has to travel with them: the library with
-# the trellis kernels built for the smallest LDS windows kernels.h admits (SMALLWIN below; tests/test_gpu_trellis.py loads it through
-# AUGX_LIB; nothing of the product loads or ships it).  It costs three more k_trellis compiles per product build.  Only those three
+# the trellis kernels built for the smallest LDS windows kernels.h admits and the dense kernels with 8 descriptors of a block in LDS
+# (SMALLWIN below; tests/test_gpu_trellis.py and tests/test_gpu_dense.py load it through AUGX_LIB; nothing of the product loads or
+# ships it).  It costs three more k_trellis and three more k_dense compiles per product build.  Only those six
 # objects depend on the windows: decoder.o and the other families lay out nothing by them (compiled with the flags they differ from the
 # product's objects in the compilation-unit id alone, which hipcc hashes from the options; with -fuse-cuid=none they are the same
 # bytes), so everything else is the product's own object
 SWOBJ = build/obj_smallwin
 define SWRULE
-$(SWOBJ)/k_trellis_$(1).o: $(SRC)/device/k_trellis.hip $(DEVHDR) include/augx.h
+$(SWOBJ)/k_$(1)_$(2).o: $(SRC)/device/k_$(1).hip $(DEVHDR) include/augx.h
 	@mkdir -p $(SWOBJ)
-	$(HIPCC) $(HIPFLAGS) $$(SMALLWIN) -DAUGX_TU_BLK=$(1) -c -o $$@ $$<
+	$(HIPCC) $(HIPFLAGS) $$(SMALLWIN) -DAUGX_TU_BLK=$(2) -c -o $$@ $$<
 endef
-$(foreach b,8 4 2,$(eval $(call SWRULE,$(b))))
-augustus_amd/libaugx_smallwin.so: $(HOSTOBJS) $(OBJ)/decoder.o $(filter-out $(OBJ)/k_trellis_%,$(KOBJS)) $(foreach b,8 4 2,$(SWOBJ)/k_trellis_$(b).o)
+$(foreach f,trellis dense,$(foreach b,8 4 2,$(eval $(call SWRULE,$(f),$(b)))))
+augustus_amd/libaugx_smallwin.so: $(HOSTOBJS) $(OBJ)/decoder.o $(filter-out $(OBJ)/k_trellis_% $(OBJ)/k_dense_%,$(KOBJS)) $(foreach f,trellis dense,$(foreach b,8 4 2,$(SWOBJ)/k_$(f)_$(b).o))
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $^
 
 # developer builds, objects of their own, loaded instead of the product library when AUGX_LIB names them:
@@ -93,8 +94,10 @@ build/libaugx_emu_slowq.so: tests/emu/emu.cc $(DEVHDR) include/augx.h
 	$(CXX) $(CXXFLAGS) -DAUGX_SLOWQ_AT=5 -shared -o $@ tests/emu/emu.cc
 
 # the same emulator with the smallest LDS windows of the trellis that kernels.h admits (its static_asserts next to ITEM_CAP): the reads
-# of predecessor values back from HBM and the candidates beyond the LDS staging, rare in the product, are then the common case
-SMALLWIN = -DAUGX_ITEM_CAP=1024 -DAUGX_LIST_WIN=128 -DAUGX_VIG_WIN=128
+# of predecessor values back from HBM and the candidates beyond the LDS staging, rare in the product, are then the common case; and
+# with 8 descriptors of a block of the dense kernels in LDS instead of 64 (dense.h: UDCAP): most are then read from HBM, which the
+# product's bound of 16 descriptors per base never lets happen
+SMALLWIN = -DAUGX_ITEM_CAP=1024 -DAUGX_LIST_WIN=128 -DAUGX_VIG_WIN=128 -DAUGX_UDCAP=8
 build/libaugx_emu_smallwin.so: tests/emu/emu.cc $(DEVHDR) include/augx.h
 	@mkdir -p build
 	$(CXX) $(CXXFLAGS) $(SMALLWIN) -shared -o $@ tests/emu/emu.cc

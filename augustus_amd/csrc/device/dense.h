@@ -22,6 +22,63 @@ namespace dev {
 AUGX_HD int baseClass(const BatchView &B, int p, int64_t g) { return B.cls[p] < 0 ? -1 : B.planeCls[p * MAXPL + B.gcPlane[g]]; }
 AUGX_HD double fxD(uint64_t v) { return (double)(int64_t)v * AUGX_FX_INV; }
 
+#ifdef AUGX_EMU
+// data paths of the dense kernels that the emulated pieces took (tests/test_emu_dense.py: the inputs of helpers.dense_edge_cases must
+// reach every one a fixture model can reach; helpers.DENSE_COVERAGE names them in this order).  "[3]": per caller of denseAt -- 0 a
+// record of kCand, 1 a UTR exon candidate, 2 a fixed-lag state
+enum EmuDense {
+    ED_DESC_MULTI_UNIT,   // utrPass: descriptors with more than one unit of UH * WAVE candidates
+    ED_DESC_GT_WAVES,     //   with more units than candidate wavefronts (one wavefront takes two units of it)
+    ED_MAX_TOTAL,         //   largest number of candidates of one descriptor (a maximum, not a count)
+    ED_LAST_HALF_EMPTY,   //   whose last unit has no candidate in its second half
+    ED_TOTAL_EXACT,       //   whose candidates fill their units exactly
+    ED_MAX_BLOCK_DESCS,   // largest number of descriptors of one block (a maximum)
+    ED_DESC_HBM,          // descriptors read from HBM (beyond UDCAP) by a candidate wavefront or the redo of the last base
+    ED_PRE_1,             // candidates taken from preTe of a descriptor with nPre == 1
+    ED_PRE_2,             //   nPre == 2
+    ED_PRE_3,             //   nPre == 3
+    ED_EXTRA_TF,          // candidates that are not on a site list, per list: truncated TSS windows
+    ED_EXTRA_TM,          //   truncated reverse poly-A signals
+    ED_EXTRA_FS,          //   forward 3' UTR from column 0
+    ED_EXTRA_RT,          //   reverse 5' UTR from column 0
+    ED_EXTRA_LA,          //   acceptor sites at the very end of the piece (xFirst)
+    ED_MID_1,             // utrCandPre: middle parts of one base
+    ED_MID_0,             //   of no base
+    ED_MID_NEG,           //   of negative length
+    ED_TAIL3_RIGHT,       // right-truncated 3' UTR (tail distribution)
+    ED_TAIL3_LEFT,        // left-truncated reverse 3' UTR
+    ED_AT_63,             // [3] denseAt: the oldest column read from the ring
+    ED_AT_64 = ED_AT_63 + 3, // [3] the newest column read from HBM
+    ED_NONRT_GT_NTW = ED_AT_64 + 3, // blocks with more records that are not RTERMINAL than stage 2 has threads
+    ED_MAX_RT,            // largest number of RTERMINAL records of one block (a maximum)
+    ED_REDO_CELLS,        // utr3single cells of the last base made again
+    ED_REDO_LIVE,         //   candidates of those cells with a live predecessor inside the block
+    ED_CHAIN_GENERAL,     // pieces that ran the general chainRun (a chain state with another chain state of its stage among its ancestors)
+    ED_LATEACC_FALSE,     // pieces whose late chain states could not be fed from the accumulators
+    ED_ALL_N,             // pieces of N only
+    ED_TRN_HBM,           // transition terms fetched from HBM (piece with several GC classes)
+    ED_TRN_LDS,           //   from LDS
+    ED_MAX_ANC_UTR,       // largest ancestor count of a UTR exon state with candidates (a maximum; beyond 4: the second loop)
+    ED_BT_STEP2,          // denseBacktracePiece: second and later steps of 256 bases of a chain run
+    ED_BT_RUN_BASE1,      //   chain runs that reach base 1 of the piece
+    ED_BT_UTR_CHUNKS,     //   UTR arg-max over more than one chunk of WAVE candidates
+    ED_BT_REC_CHUNKS,     //   record arg-max over more than WAVE records
+    ED_BT_TIE_EOP,        //   equal values of different predecessor ends (the larger end wins)
+    ED_BT_TIE_ANC,        //   equal values of two ancestors of one predecessor end (the lower index wins)
+    ED_BT_NEAR_PASS,      //   second passes of an arg-max (near ties are being counted)
+    ED_N
+};
+static long long g_emuDense[ED_N] = {0};
+static int g_emuDenseCaller = 0;
+#define EDC(k, v) (g_emuDense[k] += (long long)(v))
+#define EDMAX(k, v) do { if ((long long)(v) > g_emuDense[k]) g_emuDense[k] = (long long)(v); } while (0)
+#define EDCALLER(k) (g_emuDenseCaller = (k))
+#else
+#define EDC(k, v) do {} while (0)
+#define EDMAX(k, v) do {} while (0)
+#define EDCALLER(k) do {} while (0)
+#endif
+
 // =================================================================================================
 // K1 (UTR): content prefix terms and begin-site counts, one scan; signal records, end gates and the site lists
 // =================================================================================================
@@ -575,6 +632,7 @@ AUGX_HD int utrCandPre(const UCtx &X, const UDesc &D, int xi, int sitePos, doubl
     else {
         if (!haveRaw) braw = bmix + X.pfx(D.fxf, bom - 1);
         double mp;
+        EDC(mlen == 1 ? ED_MID_1 : mlen == 0 ? ED_MID_0 : ED_MID_NEG, 1);
         if (mlen == 1) mp = utrEmi1(X, D.fxf, X.clsAt(D.j), D.eom);
         else if (mlen == 0) mp = 0.0;
         else mp = D.ovl == 1 ? -mlen * T.ln2 : D.ovl == 2 ? -mlen * T.ln4 : 0.0;
@@ -585,6 +643,7 @@ AUGX_HD int utrCandPre(const UCtx &X, const UDesc &D, int xi, int sitePos, doubl
     tail3 = false;
     if ((D.kind == AUGX_K_UTR3SINGLE || D.kind == AUGX_K_UTR3TERM) && D.eobe == n - 1) tail3 = true; // right-truncated 3' UTR (:1290-1295,1369-1372)
     if (D.kind == AUGX_K_RUTR3SINGLE && begin <= 0) tail3 = true;                                     // left-truncated (:1312)
+    EDC(ED_TAIL3_RIGHT, tail3 && D.kind != AUGX_K_RUTR3SINGLE); EDC(ED_TAIL3_LEFT, tail3 && D.kind == AUGX_K_RUTR3SINGLE);
     return 1;
 }
 // (begin signal - content prefix) of site record e for the state described by D.  An acceptor site whose value changes during the
@@ -661,7 +720,12 @@ __device__ __forceinline__ USite ldUSite(const USite *p) { // two 16-byte global
 }
 #endif
 constexpr int UDW = 14;    // 64-bit words of a descriptor
-constexpr int UDCAP = 64;  // descriptors of a block staged in LDS (a block with more reads the rest from HBM)
+constexpr int UH = 2;      // candidates a lane of a UTR unit has in flight (three spill registers)
+constexpr int denseUW0(int blk) { return blk == 8 ? 3 : 1; } // densePiece: the wavefronts from this one on take the UTR units
+#ifndef AUGX_UDCAP
+#define AUGX_UDCAP 64
+#endif
+constexpr int UDCAP = AUGX_UDCAP; // descriptors of a block staged in LDS (a block with more reads the rest from HBM; tests build with 8)
 static_assert(sizeof(UDesc) == UDW * 8, "UDesc is copied word by word");
 
 // ---- descriptors of the open (end base, UTR exon state) pairs, once per decode: they depend on the sequence only, not on ln V.
@@ -757,10 +821,13 @@ struct DenseLds {
     int lenMax[9];
     const USite *siteTab[6];
 };
+static_assert(UDCAP >= 1, "AUGX_UDCAP: the staging loops copy min(count, UDCAP) descriptors; at least one");
+static_assert(sizeof(DenseLds) <= 160 * 1024, "AUGX_UDCAP: DenseLds must fit the LDS of a workgroup");
 
 // value of state a at base q for the block that begins at jb: from the ring while no base of the block has taken its column
 template <bool FWD> AUGX_KFN double denseAt(const DenseLds &L, const double *M, int S, int q, int a, int jb, int BLK) {
     if (q < 0) q = 0;
+    EDC(ED_AT_63 + g_emuDenseCaller, jb + BLK - 1 - q == WAVE - 1); EDC(ED_AT_64 + g_emuDenseCaller, jb + BLK - 1 - q == WAVE);
     if (jb + BLK - 1 - q < WAVE) return ldsLoadD(&L.ring[q & 63][a]);
     return ldCoherent(&M[(int64_t)q * S + a]);
 }
@@ -803,6 +870,7 @@ AUGX_KFN void densePiece(const DevTables &T, const BatchView &B, DenseLds &L, in
     auto H = [&](double x) __attribute__((always_inline)) -> double { if (FWD) return heat * x; return x; };
     // ln t(a -> s2), a = ancestor ai of s2, with the class of the end base (MODE 1: times the heat)
     auto trn = [&](int cc, int s2, int ai) __attribute__((always_inline)) -> double {
+        EDC(multi ? ED_TRN_HBM : ED_TRN_LDS, 1);
         if (multi) return H(gp(gTrans)[((int64_t)cc * S + (*lp(&L.anc[s2][ai]))) * S + s2]);
         return ldsLoadD(&L.tr[s2][ai]);
     };
@@ -851,6 +919,7 @@ AUGX_KFN void densePiece(const DevTables &T, const BatchView &B, DenseLds &L, in
         if (isChainKind(k) && !isEarlyChainKind(k)) { if (nCh < DCH) chS[nCh++] = s2; }
     }
     if (!anyNuc) { // all N: everything is intergenic (reference src/namgene.cc:205-226); one thread, column after column
+        EDC(ED_ALL_N, 1);
         FOR_THREADS(t) {
             if (t == 0) {
                 double v = initLn(T, initKind, synch);
@@ -867,9 +936,8 @@ AUGX_KFN void densePiece(const DevTables &T, const BatchView &B, DenseLds &L, in
     // per-thread constants of the fixed-lag step (thread = (state, base of the block))
     // stage 1: the threads below A1T make the fixed-lag states and stage the next block; the wavefronts from UW0 on take the UTR units
     // (blocks of up to 4 bases: one wavefront for the former, two (state, base) pairs per thread, seven for the latter)
-    constexpr int UW0 = BLK == 8 ? 3 : 1, A1T = UW0 * WAVE, FR = (DFIX * BLK + A1T - 1) / A1T;
+    constexpr int UW0 = denseUW0(BLK), A1T = UW0 * WAVE, FR = (DFIX * BLK + A1T - 1) / A1T;
     static_assert(BLK * NSIG <= A1T, "roles of stage 1");
-    constexpr int UH = 2; // candidates a lane of a UTR unit has in flight (three spill registers)
     TV2(int, fS2, FR); TV2(int, fLag, FR); TV2(int, fSg, FR);
     // per-thread constants of the chain runs (thread = slot): the state, its own ancestor index, whether the only chain state of its
     // stage among its ancestors is the state itself (then its run over the block is a recurrence in registers)
@@ -1030,6 +1098,9 @@ AUGX_KFN void densePiece(const DevTables &T, const BatchView &B, DenseLds &L, in
             if (!live && !((isItemKind(ka) && ka != AUGX_K_RTERMINAL) || isUtrExonKind(ka))) lateAcc = false;
         }
     }
+#ifdef AUGX_EMU
+    { bool general = false; for (int t = 0; t < nCh; t++) general = general || !cFast[t]; EDC(ED_CHAIN_GENERAL, general); EDC(ED_LATEACC_FALSE, !lateAcc); }
+#endif
     for (int b = 0; b < nBlocks; b++) {
         const int jb = b * BLK, par = b & 1;
         const int64_t gb = gb0 + b;
@@ -1037,6 +1108,8 @@ AUGX_KFN void densePiece(const DevTables &T, const BatchView &B, DenseLds &L, in
         const bool redoBlock = nUv > 0 && jb + BLK > n - 1 && jb <= n - 1; // (the block of the last base: one of its cells is made twice, below)
         const uint64_t i0 = (*lp(&L.bOff[par]));
         const uint32_t cntAll = (*lp(&L.bCnt[par][0])), cntNonRT = (*lp(&L.bCnt[par][1]));
+        EDC(ED_NONRT_GT_NTW, cntNonRT > (uint32_t)NTW); EDMAX(ED_MAX_RT, cntAll - cntNonRT);
+        if (nUv > 0) EDMAX(ED_MAX_BLOCK_DESCS, (*lp(&L.uCnt[par])));
         auto candValue = [&](const Item &I, int &dj, int &s2) __attribute__((always_inline)) -> double {
             dj = (int)(I.kp >> (KEY_BITS + 7)); s2 = (int)((I.kp >> KEY_BITS) & 127);
             if (!(I.te > AUGX_NINF)) return AUGX_NINF;
@@ -1045,6 +1118,7 @@ AUGX_KFN void densePiece(const DevTables &T, const BatchView &B, DenseLds &L, in
             if (eop >= jb && T.kind[s2] != AUGX_K_RTERMINAL && !isFixedKind(T.kind[I.src & 127u]) && getenv("AUGX_EMU_CHECK_LAG"))
                 fprintf(stderr, "emu: in-block predecessor that is not a fixed-lag state: state %d kind %d j %d eop %d jb %d src %d\n", s2, T.kind[s2], jb + dj, eop, jb, (int)(I.src & 127u));
 #endif
+            EDCALLER(0);
             const double pv = denseAt<FWD>(L, M, S, eop, (int)(I.src & 127u), jb, BLK);
             return pv + H(I.te);
         };
@@ -1062,7 +1136,7 @@ AUGX_KFN void densePiece(const DevTables &T, const BatchView &B, DenseLds &L, in
         // the UTR exon candidates of the block: its descriptors (kUtrDesc) are cut into units of 128 candidates, the units dealt to the
         // candidate wavefronts; within a unit the descriptor is the same for every lane, a lane takes two candidates and has the
         // loads of both in flight before it needs either (only >= 0: that one descriptor only)
-        auto utrPass = [&](bool sumPass, int only, bool defer) __attribute__((always_inline)) {
+        auto utrPass = [&](bool sumPass, int only) __attribute__((always_inline)) {
             const uint32_t nd = (uint32_t)uni((int)(*lp(&L.uCnt[par])));
             const uint64_t uo = (*lp(&L.uOff[par]));
             FOR_WAVES(w) {
@@ -1073,8 +1147,16 @@ AUGX_KFN void densePiece(const DevTables &T, const BatchView &B, DenseLds &L, in
                         const int nun = (total + UH * WAVE - 1) / (UH * WAVE);
                         const int mine = (int)((uint32_t)(w - UW0 + (NWAVES - UW0) - (int)(wi % (NWAVES - UW0))) % (NWAVES - UW0)); // first unit of this descriptor that is this wavefront's
                         wi += (uint32_t)nun;
+#ifdef AUGX_EMU
+                        if (w == UW0 && !sumPass && only < 0) { // (once per descriptor)
+                            EDC(ED_DESC_MULTI_UNIT, nun > 1); EDC(ED_DESC_GT_WAVES, nun > NWAVES - UW0); EDMAX(ED_MAX_TOTAL, total);
+                            EDC(ED_LAST_HALF_EMPTY, total > 0 && (total - 1) % (UH * WAVE) < WAVE); EDC(ED_TOTAL_EXACT, total > 0 && total % (UH * WAVE) == 0);
+                        }
+#endif
                         if (mine >= nun) continue;
+                        EDC(ED_DESC_HBM, d >= (uint32_t)UDCAP);
                         const UDesc D = d < (uint32_t)UDCAP ? *(const UDesc *)&L.ud[par][d * UDW] : B.ud[uo + d];
+                        EDMAX(ED_MAX_ANC_UTR, (*lp(&L.nanc[D.s])));
                         const int s2 = D.s, dj = D.j - jb, cc = clsAt(D.j), na = (*lp(&L.nanc[s2]));
                         const USite *sites = (*lp(&L.siteTab[D.list]));
                         const int lsel = D.len;
@@ -1092,6 +1174,7 @@ AUGX_KFN void densePiece(const DevTables &T, const BatchView &B, DenseLds &L, in
                                     utrCandIndex(D, idx, li, xi[h]);
                                     lis[h] = li;
                                     pre[h] = act[h] && xi[h] < 0 && li < D.nPre;
+                                    if (!sumPass && only < 0) { EDC(pre[h] ? ED_PRE_1 + D.nPre - 1 : ED_PRE_1, pre[h]); EDC(ED_EXTRA_TF + (D.list == UL_TF ? 0 : D.list == UL_TM ? 1 : D.list == UL_FS ? 2 : D.list == UL_RT ? 3 : 4), act[h] && xi[h] >= 0); }
                                     sPos[h] = 0; sB[h] = AUGX_NINF;
                                     if (act[h] && xi[h] < 0 && !pre[h]) {
                                         USite e;
@@ -1099,7 +1182,7 @@ AUGX_KFN void densePiece(const DevTables &T, const BatchView &B, DenseLds &L, in
                                         sPos[h] = e.pos; sB[h] = utrSiteB(B, D, e);
                                     }
                                 }
-                                // the length terms (they depend on the site's position); the rare cases go to the list of stage 2
+                                // the length terms (they depend on the site's position)
                                 _Pragma("unroll") for (int h = 0; h < UH; h++) {
                                     lnLen[h] = AUGX_NINF;
                                     if (pre[h]) { // (evaluated by the descriptor kernel)
@@ -1108,7 +1191,7 @@ AUGX_KFN void densePiece(const DevTables &T, const BatchView &B, DenseLds &L, in
                                         lnLen[h] = 0.0;
                                         act[h] = sig[h] > AUGX_NINF;
                                     } else if (act[h]) {
-                                        const int r = utrCandPre(UX, D, xi[h], sPos[h], sB[h], sig[h], len[h], tail3[h], eop[h], defer);
+                                        const int r = utrCandPre(UX, D, xi[h], sPos[h], sB[h], sig[h], len[h], tail3[h], eop[h]);
                                         act[h] = r == 1;
                                     }
                                     if (act[h] && !pre[h]) { // (utrLenAt, from the tables in LDS)
@@ -1118,6 +1201,7 @@ AUGX_KFN void densePiece(const DevTables &T, const BatchView &B, DenseLds &L, in
                                 }
                                 // the predecessors' values: every load in flight before the first is used
                                 double pv[UH][4];
+                                EDCALLER(1);
                                 _Pragma("unroll") for (int h = 0; h < UH; h++)
                                     _Pragma("unroll") for (int ai = 0; ai < 4; ai++)
                                         pv[h][ai] = (act[h] && ai < na) ? denseAt<FWD>(L, M, S, eop[h], (*lp(&L.anc[s2][ai])), jb, BLK) : AUGX_NINF;
@@ -1130,6 +1214,7 @@ AUGX_KFN void densePiece(const DevTables &T, const BatchView &B, DenseLds &L, in
                                     const double te = H(sig[h] + lnLen[h]); // (the whole emission of the candidate, pre-evaluated ones included)
                                     if (!(te > AUGX_NINF)) continue;
 #ifdef AUGX_EMU
+                                    if (eop[h] >= jb && only >= 0 && !sumPass) { bool live = false; for (int ai = 0; ai < na && ai < 4; ai++) live = live || pv[h][ai] > AUGX_NINF; EDC(ED_REDO_LIVE, live); }
                                     if (eop[h] >= jb && only < 0 && getenv("AUGX_EMU_CHECK_LAG")) fprintf(stderr, "emu: in-block predecessor of a UTR exon: state %d j %d eop %d jb %d\n", s2, D.j, eop[h], jb);
 #endif
                                     _Pragma("unroll") for (int ai = 0; ai < 4; ai++) {
@@ -1194,6 +1279,7 @@ AUGX_KFN void densePiece(const DevTables &T, const BatchView &B, DenseLds &L, in
                     if (j - lag >= 0 && emi > AUGX_NINF) {
                         const int cc = clsAt(j), na = (*lp(&L.nanc[s2]));
                         for (int ai = 0; ai < na; ai++) {
+                            EDCALLER(2);
                             const double pv = denseAt<FWD>(L, M, S, j - lag, (*lp(&L.anc[s2][ai])), jb, BLK);
                             if (!(pv > AUGX_NINF)) continue;
                             const double x = pv + (trn(cc, s2, ai) + emi);
@@ -1207,7 +1293,7 @@ AUGX_KFN void densePiece(const DevTables &T, const BatchView &B, DenseLds &L, in
             }
         }
         DPROF(1);
-        if (nUv > 0) utrPass(false, -1, false);
+        if (nUv > 0) utrPass(false, -1);
         BLOCK_SYNC();
         DPROF(2);
         // ---- 2: the records of kCand but RTERMINAL (their predecessors: earlier blocks, or fixed-lag states of this one); the early chain
@@ -1216,7 +1302,7 @@ AUGX_KFN void densePiece(const DevTables &T, const BatchView &B, DenseLds &L, in
         FOR_THREADS(t) { if (t >= WAVE && t - WAVE < nEarly * BLK) chainOthers((t - WAVE) / BLK, (t - WAVE) % BLK, jb, par, false); }
         BLOCK_SYNC();
         DPROF(3);
-        if (FWD) { itemPass(0, cntNonRT, true); if (nUv > 0) utrPass(true, -1, false); BLOCK_SYNC(); }
+        if (FWD) { itemPass(0, cntNonRT, true); if (nUv > 0) utrPass(true, -1); BLOCK_SYNC(); }
         DPROF(4);
         // ---- 3: the cells of the variable-length states; the early chain states over the block
         FOR_THREADS(t) {
@@ -1233,14 +1319,16 @@ AUGX_KFN void densePiece(const DevTables &T, const BatchView &B, DenseLds &L, in
             const uint32_t nd = (*lp(&L.uCnt[par]));
             const uint64_t uo = (*lp(&L.uOff[par]));
             for (uint32_t d = 0; d < nd; d++) {
+                EDC(ED_DESC_HBM, d >= (uint32_t)UDCAP);
                 const UDesc D = d < (uint32_t)UDCAP ? *(const UDesc *)&L.ud[par][d * UDW] : B.ud[uo + d];
                 if (D.kind != AUGX_K_UTR3SINGLE || D.j != n - 1 || D.total == 0) continue;
+                EDC(ED_REDO_CELLS, 1);
                 const int s2 = D.s;
                 FOR_THREADS(t) { if (t == 0) { (*lp(&L.cmax[par][n - 1 - jb][s2])) = AUGX_NINF; (*lp(&L.csum[par][n - 1 - jb][s2])) = 0ull; } }
                 BLOCK_SYNC();
-                utrPass(false, (int)d, false);
+                utrPass(false, (int)d);
                 BLOCK_SYNC();
-                if (FWD) { utrPass(true, (int)d, false); BLOCK_SYNC(); }
+                if (FWD) { utrPass(true, (int)d); BLOCK_SYNC(); }
                 FOR_THREADS(t) {
                     if (t == 0) {
                         double f = (*lp(&L.cmax[par][n - 1 - jb][s2]));
@@ -1341,6 +1429,7 @@ AUGX_KFN void denseBacktracePiece(const DevTables &T, const BatchView &B, int p)
                     break;
                 }
                 cur -= 4 * WAVE;
+                EDC(ED_BT_STEP2, 1);
             }
             if (B.nearTie) { // the cells of this run whose decision (stay / come in from another state) was a near tie
                 for (int q0 = cur < 1 ? 1 : cur; q0 <= base; q0 += WAVE) {
@@ -1349,6 +1438,7 @@ AUGX_KFN void denseBacktracePiece(const DevTables &T, const BatchView &B, int p)
                     nearTies += waveCount(fl);
                 }
             }
+            EDC(ED_BT_RUN_BASE1, cur < 1);
             if (cur < 1) { eop = 0; ai = -1; }
             else if (w == 0xFE) { eop = 0; ai = -1; } // (a piece of N only: intergenic from the first base)
             else { eop = cur - 1; ai = w; }
@@ -1362,6 +1452,7 @@ AUGX_KFN void denseBacktracePiece(const DevTables &T, const BatchView &B, int p)
             const int cc = UX.clsAt(base);
             Best best{AUGX_NINF, -2147483647, -1};
             double runnerUp = AUGX_NINF; // (pass 1, only when near ties are counted: the largest (predecessor end, ancestor) that is not the winner)
+            EDC(ED_BT_UTR_CHUNKS, D.total > WAVE); EDC(ED_BT_NEAR_PASS, B.nearTie != nullptr);
             for (int pass = 0; pass < (B.nearTie ? 2 : 1); pass++)
             for (int c0 = 0; c0 < D.total; c0 += WAVE) {
                 LV(double, cv); LV(int, ck); LV(int, ca);
@@ -1374,10 +1465,14 @@ AUGX_KFN void denseBacktracePiece(const DevTables &T, const BatchView &B, int p)
                             if (!(pv > AUGX_NINF)) continue;
                             if (pass == 1 && e2 + KEY_BIAS == best.key && a2 == best.aux) continue; // (the winner itself)
                             const double v = pv + (lnT(T, cc, T.anc[state][a2], state) + te);
+                            EDC(ED_BT_TIE_ANC, pass == 0 && v == LX(cv));
                             if (v > LX(cv)) { LX(cv) = v; LX(ck) = e2 + KEY_BIAS; LX(ca) = a2; }
                         }
                 }
                 const Best b2 = waveArgMax(cv, ck, ca);
+#ifdef AUGX_EMU
+                if (pass == 0 && b2.v > AUGX_NINF) { int same = b2.v == best.v; for (int l2 = 0; l2 < WAVE; l2++) same += cv[l2] == b2.v; EDC(ED_BT_TIE_EOP, same > 1); }
+#endif
                 if (pass == 0) { if (better(b2.v, b2.key, best.v, best.key)) best = b2; }
                 else if (b2.v > runnerUp) runnerUp = b2.v;
             }
@@ -1391,6 +1486,7 @@ AUGX_KFN void denseBacktracePiece(const DevTables &T, const BatchView &B, int p)
             const uint32_t cnt = B.blkCnt[gb * 2 + 1], pid = (uint32_t)(((base % blkSz) << 7) | state);
             Best best{AUGX_NINF, -2147483647, -1};
             double runnerUp = AUGX_NINF;
+            EDC(ED_BT_REC_CHUNKS, cnt > (uint32_t)WAVE); EDC(ED_BT_NEAR_PASS, B.nearTie != nullptr);
             for (int pass = 0; pass < (B.nearTie ? 2 : 1); pass++)
             for (uint32_t c0 = 0; c0 < cnt; c0 += WAVE) {
                 LV(double, cv); LV(int, ck); LV(int, ca);
@@ -1413,6 +1509,9 @@ AUGX_KFN void denseBacktracePiece(const DevTables &T, const BatchView &B, int p)
                     }
                 }
                 const Best b2 = waveArgMax(cv, ck, ca);
+#ifdef AUGX_EMU
+                if (pass == 0 && b2.v > AUGX_NINF) { int same = b2.v == best.v; for (int l2 = 0; l2 < WAVE; l2++) same += cv[l2] == b2.v; EDC(ED_BT_TIE_EOP, same > 1); }
+#endif
                 if (pass == 0) { if (better(b2.v, b2.key, best.v, best.key)) best = b2; }
                 else if (b2.v > runnerUp) runnerUp = b2.v;
             }

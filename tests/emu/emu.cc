@@ -435,6 +435,18 @@ int emu_slowq_at() { return SLOWQ_AT; }
 // entries; ET_FWD_MAX_CELL is a maximum)
 int emu_trellis_coverage(long long *out) { for (int i = 0; i < ET_N; i++) out[i] = g_emuTrellis[i]; return ET_N; }
 void emu_trellis_coverage_reset() { for (int i = 0; i < ET_N; i++) g_emuTrellis[i] = 0; }
+// data paths of the dense kernels taken since the last reset (dense.h: EmuDense, ED_N entries; the ED_MAX_* are maxima)
+int emu_dense_coverage(long long *out) { for (int i = 0; i < ED_N; i++) out[i] = g_emuDense[i]; return ED_N; }
+void emu_dense_coverage_reset() { for (int i = 0; i < ED_N; i++) g_emuDense[i] = 0; }
+// what the dense kernels derive from the build for block size blk: descriptors of a block staged in LDS (AUGX_UDCAP), candidates of a
+// unit, candidate wavefronts, threads of the record passes (NTW), bases per step of the back-trace's chain runs
+void emu_dense_dims(int blk, int *out) { out[0] = UDCAP; out[1] = UH * WAVE; out[2] = NWAVES - denseUW0(blk); out[3] = NT - WAVE; out[4] = 4 * WAVE; }
+// how far the fixed-lag states of the model look back, as densePiece has it: the longdss, the longass and the equalD states
+void emu_dense_lags(const augx_tables *t, int *out) {
+    DevTables D;
+    fillDevTablesScalars(*t, D);
+    out[0] = D.Ds + 2 + D.De; out[1] = D.As + 2 + D.Ae + D.U; out[2] = D.dStateLen;
+}
 // lengths of the model the conditions of the tests rest on: intron d, maxexonlength, W, dStateLen as the kernels get it
 // (layout.h: fillDevTablesScalars), the GC classes, and the most candidates one forward cell can have (layout.h: forwardCellCandidates)
 void emu_model_dims(const augx_tables *t, long long *out) {

@@ -898,3 +898,121 @@ def trellis_edge_long(n=390000):
         s = s[:at] + block + s[at + len(block):]
     assert len(s) == n
     return s
+
+
+# ---------------------------------------------------------------------------------------------------
+# the rare data paths of the dense kernels (tests/test_emu_dense.py, tests/test_gpu_dense.py)
+# ---------------------------------------------------------------------------------------------------
+# dense.h: EmuDense, in the order of the emulator's counters ("at63_k" / "at64_k": per caller of denseAt, 0 a record of kCand, 1 a UTR
+# exon candidate, 2 a fixed-lag state)
+DENSE_COVERAGE = (("desc_multi_unit", "desc_gt_waves", "max_total", "last_half_empty", "total_exact", "max_block_descs", "desc_hbm",
+                   "pre_1", "pre_2", "pre_3", "extra_tf", "extra_tm", "extra_fs", "extra_rt", "extra_la", "mid_1", "mid_0", "mid_neg",
+                   "tail3_right", "tail3_left") + tuple("at63_%d" % i for i in range(3)) + tuple("at64_%d" % i for i in range(3))
+                  + ("nonrt_gt_ntw", "max_rt", "redo_cells", "redo_live", "chain_general", "lateacc_false", "all_n", "trn_hbm", "trn_lds",
+                     "max_anc_utr", "bt_step2", "bt_run_base1", "bt_utr_chunks", "bt_rec_chunks", "bt_tie_eop", "bt_tie_anc", "bt_near_pass"))
+DENSE_MAXIMA = ("max_total", "max_block_descs", "max_rt", "max_anc_utr")  # (maxima, not counts)
+
+
+def emu_dense_coverage(lib=None, reset=False):
+    """{counter: value} of the data paths the dense kernels (dense.h: densePiece, denseBacktracePiece) took in the emulator `lib` since
+    its last reset (DENSE_MAXIMA: maxima); reset=True clears them afterwards"""
+    E = _emu_of(lib)
+    out = (ctypes.c_longlong * 128)()
+    n = E.emu_dense_coverage(out)
+    assert n == len(DENSE_COVERAGE), n
+    if reset:
+        E.emu_dense_coverage_reset()
+    return dict(zip(DENSE_COVERAGE, out[:n]))
+
+
+def emu_dense_coverage_reset(lib=None):
+    _emu_of(lib).emu_dense_coverage_reset()
+
+
+def emu_dense_dims(blk, lib=None):
+    """what the dense kernels of the emulator `lib` derive from the build at block size blk: {UDCAP: descriptors of a block staged in
+    LDS, UNIT: candidates of a unit (UH * WAVE), CAND_WAVES: candidate wavefronts, NTW: threads of the record passes, BT_STEP: bases
+    per step of a chain run of the back-trace}"""
+    out = (ctypes.c_int * 8)()
+    _emu_of(lib).emu_dense_dims(blk, out)
+    return dict(zip(("UDCAP", "UNIT", "CAND_WAVES", "NTW", "BT_STEP"), out[:5]))
+
+
+def emu_dense_lags(tables_ptr, lib=None):
+    """how far the fixed-lag states of a loaded model look back in densePiece: (longdss, longass, equalD)"""
+    out = (ctypes.c_int * 4)()
+    _emu_of(lib).emu_dense_lags(tables_ptr, out)
+    return tuple(out[:3])
+
+
+DENSE_PREFIX_LENS = (1, 2, 3, 4, 5, 7, 31, 32, 33, 63, 64, 65, 127, 129, 1022, 1023, 1024, 1025)
+# (index of a state of the twin's path of HS04636 under the human model with UTR states, bases behind its end at which the record is cut)
+_DENSE_CUTS = ((3, 0), (5, 1), (11, 1), (14, 3), (19, 5), (28, 4), (34, 0), (41, 1))
+_dense_cases = None
+
+
+def dense_edge_cases():
+    """[(name, sequence)] made for the data paths of the dense kernels that ordinary DNA rarely takes (dense.h: densePiece, utrPass,
+    denseBacktracePiece); tests/test_emu_dense.py asserts from the emulator's counters (EmuDense) that they take them.  Found by a
+    search over motifs driven by those counters; every record is 25 kb or shorter.
+    - cag_dense: 2500 acceptor sites three bases apart: UTR exon cells with up to 1157 candidates under the human model -- descriptors of
+      more units of 128 candidates than there are candidate wavefronts, so that a wavefront takes two units of one descriptor;
+    - taa_after_gene, aataaa_after_gene: a gene, then stop codons / poly-A signals at every third (sixth) base: 3' UTR exons with up to
+      1833 candidates, right- and left-truncated 3' UTRs (the tail distribution), the descriptors' pre-evaluated candidates (nPre 1..3);
+    - tttatt: reverse poly-A signals: candidates that are truncated reverse signals, two ancestors of one predecessor end with equal value;
+    - cat_dense, ac_tta: reverse acceptors / an AC stretch then reverse stops: middle parts of length 1, 0 and below 0, blocks with more
+      records than the record passes have threads; ac_tta has two GC classes under the human model;
+    - cag_many (helpers.trellis_edge_cases) and its reverse complement: 3990 in-frame acceptors before one donor site;
+    - cut_*: the golden record HS04636 cut a few bases behind the end of a state of the oracle twin's path: the right-truncated 3' UTR
+      cell of the last base is made again from predecessors of its own block (redoBlock), which are alive there;
+    - prefix_n: the first n bases of HS04636 for the n of DENSE_PREFIX_LENS: the edges of a block (2, 4, 8), of the 32 bases of a group
+      of the descriptor kernel, of the ring of 64 columns and of a chunk of 1024 slots;
+    - N_1, N_2, N_5, N_300: pieces of N only (short-circuited by densePiece); gene_N_runs: HS04636 with runs of 1, 2, 5 and 300 N in it;
+    - twoclass_gene: HS04636 between a stretch of low and one of high GC content: two GC classes under the human model, the transition
+      terms of every cell come from HBM"""
+    global _dense_cases
+    if _dense_cases is not None:
+        return list(_dense_cases)
+    import augustus_amd as ax
+    by = dict(golden_inputs())
+    gene = by["HS04636"]
+    tr = dict(trellis_edge_cases())
+    acgt = "ACGT" * 500
+    recs = [
+        ("cag_dense", acgt + "CAG" * 2500 + acgt),
+        ("taa_after_gene", gene + "TAA" * 2500),
+        ("tttatt", "TTTATT" * 1200),
+        ("aataaa_after_gene", gene + "AATAAA" * 1200),
+        ("cat_dense", acgt + "CAT" * 2500 + acgt),
+        ("ac_tta", random_dna(6000, 5, "AC") + "TTA" * 1500),
+        ("cag_many", tr["cag_many"]),
+        ("cag_many_rc", revcomp(tr["cag_many"])),
+    ]
+    m = ax.Model(config_path(), "human", UTR="on")
+    rc, _, path, _, _ = twin_decode(m.tables_ptr, gene, m.n_states)
+    assert rc == 0 and len(path) > max(i for i, _ in _DENSE_CUTS), len(path)
+    assert len(_DENSE_CUTS) <= 16
+    for i, k in _DENSE_CUTS:
+        n = path[i][1] + 1 + k  # (path: 1-based begin and end of the state = index of its last base)
+        assert 2 <= n <= len(gene)
+        recs.append(("cut_%d_%d" % (i, k), gene[:n]))
+    recs += [("prefix_%d" % n, gene[:n]) for n in DENSE_PREFIX_LENS]
+    recs += [("N_%d" % n, "N" * n) for n in (1, 2, 5, 300)]
+    recs.append(("gene_N_runs", gene[:3000] + "N" + gene[3001:5000] + "NN" + gene[5002:6000] + "N" * 5 + gene[6005:7000] + "N" * 300 + gene[7300:]))
+    recs.append(("twoclass_gene", _gc_dna(7000, 0.30, 9101) + gene + _gc_dna(7000, 0.66, 9102)))
+    assert max(len(s) for _, s in recs) <= 25000 and len(recs) <= 42
+    _dense_cases = recs
+    return list(recs)
+
+
+BACKTRACE_EDGE_LENS = sorted(set(range(1, 301)) | {256 * k + d for k in range(1, 32) for d in (-1, 0, 1, 2)})
+
+
+def dense_backtrace_prefixes(kmax=31):
+    """[(name, sequence)]: the first n bases of the golden record softmask_all for n = 1..300 and n = 256 k + d, k = 1..kmax, d in
+    {-1, 0, 1, 2}: one intergenic run of n - 1 bases under the models of tests/test_emu_dense.py (the caller asserts that from the twin's
+    path): the chain runs of denseBacktracePiece that end on, one before and one after the last base of a step of 256, and at base 1"""
+    src = dict(golden_inputs())["softmask_all"]
+    lens = [n for n in BACKTRACE_EDGE_LENS if n <= 256 * kmax + 2]
+    assert len(src) >= lens[-1]
+    return [("softmask_all[:%d]" % n, src[:n]) for n in lens]

@@ -1,6 +1,8 @@
 """GPU parity of the 71-state model with untranslated regions (--UTR=on: dense kernels, device/dense.h), through the C ABI.
 Checkers: the oracle twin (oracle/ghmm_twin.cc, pinned to the real reference cell by cell in tests/test_oracle.py) and the
-golden vectors made from the real reference (tests/golden/make_golden.py: the `human_utr`, `fly_utr`, ... configurations)."""
+golden vectors made from the real reference (tests/golden/make_golden.py: the `human_utr`, `fly_utr`, ... configurations).
+These are end-to-end runs on golden records and random DNA; the inputs made for the rare data paths of the dense kernels (units beyond
+the candidate wavefronts, the ring edge, the cell made twice, the back-trace's steps) are in tests/test_gpu_dense.py."""
 import os
 
 import numpy as np
