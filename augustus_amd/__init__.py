@@ -79,6 +79,10 @@ def lib():
         L.augx_batch_cells.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
         L.augx_batch_prep.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
                                       ctypes.POINTER(ctypes.c_int64)]
+        L.augx_batch_replay_counters.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_longlong)]
+        L.augx_batch_replay_patches.restype = L.augx_batch_replay_sites.restype = ctypes.c_int64
+        L.augx_batch_replay_patches.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]
+        L.augx_batch_replay_sites.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]
         L.augx_batch_kernel_ms.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_float),
                                            ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
         _plan = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
@@ -245,6 +249,20 @@ class Batch:
         decode left it, plane ``plane`` of the arrays that have one per GC class of the piece (fx, plsR)"""
         L = lib()
         return prep_fetch(lambda w, pl, out, cap, nb: L.augx_batch_prep(self.decoder._h, self._h, piece, w, pl, out, cap, nb), which, plane)
+
+    def replay_hooks(self):
+        """test hooks (``augx_batch_replay_counters`` / ``_patches`` / ``_sites``; decoder created with AUGX_DEBUG_CELLS=1): three callables
+        of the shape of the test emulator's exports, bound to this batch.  A refusal raises."""
+        L, dh, bh = lib(), self.decoder._h, self._h
+
+        def checked(f):
+            def g(*a):
+                r = f(dh, bh, *a)
+                if r < 0:
+                    _check(r)
+                return r
+            return g
+        return checked(L.augx_batch_replay_counters), checked(L.augx_batch_replay_patches), checked(L.augx_batch_replay_sites)
 
     def plan(self):
         """``augx_batch_plan``: the plan of the trellis passes this batch was created with (see :func:`plan_segments`) and, once it has

@@ -27,6 +27,19 @@ namespace dev {
 struct AssHist { int32_t site; uint32_t key; int32_t pl; }; // the value of `site` is computed with the class of plane `pl` by the call of (column, state) = (key >> 7, key & 127)
 AUGX_HD uint32_t assKey(int j, int s) { return ((uint32_t)j << 7) | (uint32_t)s; }
 
+// which of its paths a replay took (plain adds, always compiled; tests/test_emu_replay.py proves that the test inputs reach them)
+enum AssCount {
+    AC_CALLS, AC_FLUSHES, AC_SKIPS, AC_SKIPPED_SITES, AC_FLUSH_IN_SKIP,
+    AC_FIRST_LONGASS, AC_FIRST_UTR5INTERNAL, AC_FIRST_UTR5TERM, AC_FIRST_UTR3INTERNAL, AC_FIRST_UTR3TERM,
+    AC_LONG_FOREIGN, AC_SITES_0CHANGES, AC_SITES_1CHANGE, AC_SITES_2CHANGES, AC_EXTRAS, AC_LATE_CALLS, AC_LATE_FLUSHES,
+    AC_VIT_DIFFS, // (sampler.h: SamplePiece::memoVitDiffs, copied in by whoever runs the sampler beside the memo)
+    AC_N
+};
+struct AssCounters {
+    long long c[AC_N] = {0};
+    void add(const AssCounters &o) { for (int i = 0; i < AC_N; i++) c[i] += o.c[i]; }
+};
+
 struct AssMemoReplay {
     static constexpr int MEMO_MAX = 1000; // memoF.size() > 1000 -> emptied
     const DevTables *T = nullptr;
@@ -45,6 +58,7 @@ struct AssMemoReplay {
     std::vector<AssHist> hist;            // in the order of the calls; a re-computation with the class the site had before is left out
     std::vector<int8_t> longCls;          // [site] plane the longass states of column q get their value from (-1: they do not ask)
     long long flushes = 0, calls = 0;
+    mutable AssCounters stats;            // (calls and flushes of the sweep are copied in when it ends; `extras` by patches())
     // the memo as the sweep leaves it: it lives on through the back-tracking of the Viterbi path and the sampled paths of the piece
     // (reference NAMGene::getViterbiPath / getSampledPath, src/namgene.cc:432-510,366-424: every step through a longass state or one of
     // the four UTR exon kinds asks again, with the class of the step's end base; sampler.h)
@@ -54,8 +68,8 @@ struct AssMemoReplay {
     std::vector<int32_t> histFirst;       // [site + 1] its entries of histBy (time order)
     std::vector<AssHist> histBy;
     int late(int i, int pl) {             // a call after the sweep: the plane the value comes from
-        calls++;
-        if (count > MEMO_MAX) { E++; count = 0; flushes++; }
+        calls++; stats.c[AC_LATE_CALLS]++;
+        if (count > MEMO_MAX) { E++; count = 0; flushes++; stats.c[AC_LATE_FLUSHES]++; }
         if (epochOf[(size_t)i] == E) return clsOf[(size_t)i];
         epochOf[(size_t)i] = E; count++; clsOf[(size_t)i] = (int8_t)pl;
         return pl;
@@ -70,6 +84,10 @@ struct AssMemoReplay {
         return it != siteQ.end() && *it == q ? (int)(it - siteQ.begin()) : -1;
     }
 
+    static int firstAsker(int kind) {
+        return kind == AUGX_K_LONGASS ? AC_FIRST_LONGASS : kind == AUGX_K_UTR5INTERNAL ? AC_FIRST_UTR5INTERNAL : kind == AUGX_K_UTR5TERM ? AC_FIRST_UTR5TERM
+             : kind == AUGX_K_UTR3INTERNAL ? AC_FIRST_UTR3INTERNAL : AC_FIRST_UTR3TERM;
+    }
     static bool asks(int kind) { return kind == AUGX_K_LONGASS || kind == AUGX_K_UTR5INTERNAL || kind == AUGX_K_UTR5TERM || kind == AUGX_K_UTR3INTERNAL || kind == AUGX_K_UTR3TERM; }
     void requesters() {
         nReq = 0;
@@ -98,12 +116,14 @@ struct AssMemoReplay {
             for (int h = h0 + 1; h < h1; h++) sw.push_back({by[(size_t)h].key, by[(size_t)h].pl});
             out.push_back(A);
         }
+        stats.c[AC_EXTRAS] = extras;
         return extras;
     }
 
     // slow: every call is made (no use of what is known to be in the memo) -- the plain restatement, for tests
     void run(bool slow = false) {
         hist.clear(); flushes = 0; calls = 0;
+        stats = AssCounters();
         const int nS = (int)siteQ.size(), off = T->U + T->As + 2 + T->Ae;
         longCls.assign((size_t)nS, -1);
         epochOf.assign((size_t)nS, -1);
@@ -124,6 +144,7 @@ struct AssMemoReplay {
                     if (count > MEMO_MAX) { E++; count = 0; flushes++; }
                     if (epochOf[(size_t)i] == E) return;
                     epochOf[(size_t)i] = E; count++;
+                    stats.c[firstAsker(reqKind[r])]++;
                     if (clsOf[(size_t)i] != c) { clsOf[(size_t)i] = (int8_t)c; hist.push_back({i, assKey(j, reqS[r]), c}); }
                 };
                 if (reqKind[r] == AUGX_K_LONGASS) {
@@ -143,7 +164,7 @@ struct AssMemoReplay {
                 // in the memo: those calls change nothing -- unless the memo is full, then the first of them empties it
                 int flushedAt = -1;
                 for (int i = iHi; i >= iLo;) {
-                    if (!slow && cE[r] == E && i >= cLo[r] && i <= cHi[r] && count <= MEMO_MAX) { i = cLo[r] - 1; continue; }
+                    if (!slow && cE[r] == E && i >= cLo[r] && i <= cHi[r] && count <= MEMO_MAX) { stats.c[AC_SKIPS]++; stats.c[AC_SKIPPED_SITES] += i - cLo[r] + 1; i = cLo[r] - 1; continue; }
                     if ((siteAlive[(size_t)i] >> r) & 1) {
                         const int e0 = E;
                         call(i);
@@ -151,6 +172,7 @@ struct AssMemoReplay {
                     }
                     i--;
                 }
+                if (flushedAt >= 0) stats.c[AC_FLUSH_IN_SKIP]++;
                 cLo[r] = iLo; cHi[r] = flushedAt >= 0 ? flushedAt : iHi; cE[r] = E;
             }
         }
@@ -159,6 +181,13 @@ struct AssMemoReplay {
         for (int i = 0; i < nS; i++) histFirst[(size_t)i + 1] += histFirst[(size_t)i];
         histBy.resize(hist.size());
         { std::vector<int32_t> w(histFirst.begin(), histFirst.end() - 1); for (const AssHist &h : hist) histBy[(size_t)w[(size_t)h.site]++] = h; } // (stable: time order within a site)
+        stats.c[AC_CALLS] = calls; stats.c[AC_FLUSHES] = flushes;
+        for (int i = 0; i < nS; i++) {
+            const int k = histFirst[(size_t)i + 1] - histFirst[(size_t)i];
+            if (k >= 1) stats.c[k == 1 ? AC_SITES_0CHANGES : k == 2 ? AC_SITES_1CHANGE : AC_SITES_2CHANGES]++;
+            const int q = siteQ[(size_t)i];
+            if (longCls[(size_t)i] >= 0 && longCls[(size_t)i] != plane[q < n ? q : n - 1]) stats.c[AC_LONG_FOREIGN]++;
+        }
     }
 };
 

@@ -36,6 +36,7 @@
 #include "layout.h"
 #include "launch.h"
 #include "assmemo.h"
+#include "snipmemo.h"
 #include "../capi_internal.h"
 
 using namespace augx;
@@ -364,16 +365,17 @@ __global__ void __launch_bounds__(256) kTssReplay(const DevTables *__restrict__ 
     if (B.nPlanes[p] <= 1 || B.cls[p] < 0) return;
     if (k1TssReplay(*T, B, p, li, mat + (B.off[p] + 1) * T->S)) atomicAdd(changed, 1);
 }
-// what the replay of the aSSProb memo reads: per acceptor site (entry listOffs[p] + 8 p + li; 8 more entries per piece for the sites
-// past its end) q and the aliveness bits, per slot the end-gate bits of the asking UTR exon states
+// what the replay of the aSSProb memo reads: per acceptor site (entry listOffs[p] + ASS_PAST_END p + li; ASS_PAST_END = 8 more entries per
+// piece for the sites past its end: layout.h, chooseDenseBlock refuses a model with more) q and the aliveness bits, per slot the
+// end-gate bits of the asking UTR exon states
 __global__ void __launch_bounds__(256) kMemoSites(const DevTables *__restrict__ T, BatchView B, const double *mat, MemoReq rq, int32_t *siteQ, uint8_t *alive) {
     const int p = blockIdx.y, li = blockIdx.x * 256 + threadIdx.x;
     if (B.nPlanes[p] <= 1 || B.cls[p] < 0) return;
     const int nList = (int)B.cnt[fidx(B.off[p] + B.len[p], CNT_LA, NCNT)];
-    if (li >= nList + 8) return;
+    if (li >= nList + ASS_PAST_END) return;
     uint8_t a = 0;
     const int q = li < nList + T->Ae ? memoAssSite(*T, B, p, li, mat + (B.off[p] + 1) * T->S, rq.s, rq.n, a) : -1;
-    const int64_t i = B.listOffs[p] + 8 * (int64_t)p + li;
+    const int64_t i = B.listOffs[p] + ASS_PAST_END * (int64_t)p + li;
     siteQ[i] = q; alive[i] = a;
 }
 __global__ void __launch_bounds__(256) kMemoGates(const DevTables *__restrict__ T, BatchView B, MemoReq rq, uint8_t *gate) {
@@ -404,7 +406,6 @@ __global__ void __launch_bounds__(64) kBacktrace(const DevTables *T, BatchView B
 // (snipmemo.h) everything the replay of one piece's windows reads, packed for ONE copy to the host: the candidate records of each
 // window's blocks in block order, the intron content prefix slots of both strands and every plane, the rows of the matrix that
 // tells which cells are alive.  One workgroup per window.
-struct GatherWin { int64_t o, gb0, poolOff, fxOff, fOff; int32_t b0, b1, g0, nSlots, nPl, r0, nRows, pad; };
 __global__ void __launch_bounds__(256) kGatherWindows(BatchView V, const GatherWin *W, Item *outItems, uint64_t *outFx, const double *mat, double *outF, int S) {
     __shared__ uint32_t sc[256];
     __shared__ uint64_t running;
@@ -630,6 +631,16 @@ struct augx_batch {
     DevBuf laSwBuf;            // (dense, UTR) acceptor sites whose value changes during the sweep (BatchView::laSw)
     size_t nLaSw = 0;          // its entries
     std::vector<std::shared_ptr<augx::dev::AssMemoReplay>> memoOf; // [piece] the aSSProb memo as the sweep left it (the sampler goes on from a copy), or null
+    // test hooks (augx_batch_replay_*; kept only by a decoder created with AUGX_DEBUG_CELLS=1): what the replays of the last decode or
+    // forward run did -- the rebuilt candidate terms by (piece, j, state, eop), the history of the acceptor sites (piece, q, key, class),
+    // the counters of both replays and the TSS windows changed
+    struct SnipRec { int32_t piece, j, s, eop; double te; };
+    struct SiteRec { int32_t piece, q, key, cls; };
+    std::vector<SnipRec> dbgSnip;
+    std::vector<SiteRec> dbgSites;
+    augx::dev::SnipCounters dbgSnipStats;
+    augx::dev::AssCounters dbgAssStats;
+    long long dbgTss = 0;
 };
 
 namespace {
@@ -1422,6 +1433,38 @@ int augx_batch_cells(augx_decoder *d, augx_batch *b, int piece, double *out) {
     return AUGX_OK;
 }
 
+static bool replayHookOk(augx_decoder *d, augx_batch *b, const char *who) {
+    if (!d || !b) { setLastError(std::string(who) + ": NULL argument"); return false; }
+    if (!d->debugCells) { setLastError(std::string(who) + ": decoder was not created with AUGX_DEBUG_CELLS=1"); return false; }
+    if (!b->decoded) { setLastError(std::string(who) + ": the batch has not been decoded"); return false; }
+    return true;
+}
+int augx_batch_replay_counters(augx_decoder *d, augx_batch *b, long long *snip, long long *ass, long long *tss) {
+    if (!replayHookOk(d, b, "augx_batch_replay_counters") || !snip || !ass || !tss) return AUGX_E_ARG;
+    for (int i = 0; i < augx::dev::SC_N; i++) snip[i] = b->dbgSnipStats.c[i];
+    for (int i = 0; i < augx::dev::AC_N; i++) ass[i] = b->dbgAssStats.c[i];
+    // (calls after the sweep -- the sampler works on a copy of the memo -- are not the batch's to count: AC_LATE_CALLS, AC_LATE_FLUSHES
+    // and AC_VIT_DIFFS are always 0 here)
+    *tss = b->dbgTss;
+    return augx::dev::SC_N * 100 + augx::dev::AC_N;
+}
+int64_t augx_batch_replay_patches(augx_decoder *d, augx_batch *b, int32_t *keys, double *te, int64_t cap) {
+    if (!replayHookOk(d, b, "augx_batch_replay_patches")) return AUGX_E_ARG;
+    for (int64_t i = 0; keys && te && i < cap && i < (int64_t)b->dbgSnip.size(); i++) {
+        const augx_batch::SnipRec &r = b->dbgSnip[(size_t)i];
+        keys[i * 4] = r.piece; keys[i * 4 + 1] = r.j; keys[i * 4 + 2] = r.s; keys[i * 4 + 3] = r.eop; te[i] = r.te;
+    }
+    return (int64_t)b->dbgSnip.size();
+}
+int64_t augx_batch_replay_sites(augx_decoder *d, augx_batch *b, int32_t *recs, int64_t cap) {
+    if (!replayHookOk(d, b, "augx_batch_replay_sites")) return AUGX_E_ARG;
+    for (int64_t i = 0; recs && i < cap && i < (int64_t)b->dbgSites.size(); i++) {
+        const augx_batch::SiteRec &r = b->dbgSites[(size_t)i];
+        recs[i * 4] = r.piece; recs[i * 4 + 1] = r.q; recs[i * 4 + 2] = r.key; recs[i * 4 + 3] = r.cls;
+    }
+    return (int64_t)b->dbgSites.size();
+}
+
 int augx_batch_prep(augx_decoder *d, augx_batch *b, int piece, int which, int plane, void *out, int64_t cap_bytes, int64_t *n_bytes) {
     if (!d || !b || !n_bytes || piece < 0 || piece >= b->V.nPieces || which < 0 || which >= AUGX_PREP_N) { setLastError("augx_batch_prep: bad argument"); return AUGX_E_ARG; }
     *n_bytes = 0;
@@ -1528,6 +1571,7 @@ int snippetCacheReplay(augx_decoder *d, augx_batch *b, int64_t &nPatched, bool f
     nPatched = 0;
     const BatchView &V = b->V;
     const int n = V.nPieces, S = d->hostT.S;
+    if (d->debugCells) { b->dbgSnip.clear(); b->dbgSnipStats = SnipCounters(); }
     std::vector<int32_t> nPl((size_t)n);
     HIP_TRY(hipStreamSynchronize(d->stream));
     HIP_TRY(hipMemcpy(nPl.data(), V.nPlanes, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
@@ -1608,22 +1652,9 @@ int snippetCacheReplay(augx_decoder *d, augx_batch *b, int64_t &nPatched, bool f
         R.prefetch = [=](const std::vector<std::pair<int, int>> &tt) -> int {
             const hipStream_t cst = DP->st;
             SnippetReplay &R2 = DP->R;
-            DP->wins.clear(); DP->nextWin = 0;
+            DP->nextWin = 0;
             int64_t pool = 0, fx = 0, fr = 0;
-            for (auto w : tt) {
-                int t0 = w.first < 0 ? 0 : w.first, t1 = w.second > len - 1 ? len - 1 : w.second;
-                GatherWin g;
-                memset(&g, 0, sizeof g);
-                g.o = o; g.gb0 = gb0; g.b0 = t0 / blkSz; g.b1 = t1 / blkSz;
-                g.r0 = t0 - R2.d - 2 > 0 ? t0 - R2.d - 2 : 0;
-                g.g0 = g.r0; g.nSlots = t1 + 1 - g.r0 + 1; g.nPl = nplP;
-                g.nRows = fromLists ? 0 : t1 - g.r0 + 1;
-                g.poolOff = pool; g.fxOff = fx; g.fOff = fr;
-                for (int q = g.b0; q <= g.b1; q++) pool += DP->blkCnt[(size_t)q * 2 + 1];
-                fx += (int64_t)g.nPl * 2 * g.nSlots;
-                fr += (int64_t)g.nRows * S;
-                DP->wins.push_back(g);
-            }
+            planGatherWins(tt, len, blkSz, R2.d, nplP, DP->blkCnt.data(), !fromLists, S, o, gb0, DP->wins, pool, fx, fr);
             if (DP->wins.empty()) return AUGX_OK;
             DP->poolAll.resize((size_t)pool + 1); DP->fxAll.resize((size_t)fx + 1); DP->FAll.resize((size_t)fr + 1);
             DevBuf dW, dI, dX, dF;
@@ -1647,33 +1678,7 @@ int snippetCacheReplay(augx_decoder *d, augx_batch *b, int64_t &nPatched, bool f
             return AUGX_OK;
         };
         R.fetch = [=](int ft0, int ft1) -> int { // the next window's part of what prefetch brought
-            SnippetReplay &R2 = DP->R;
-            if (DP->nextWin >= DP->wins.size()) return AUGX_E_ARG;
-            const GatherWin &g = DP->wins[DP->nextWin++];
-            {   // (the windows are handed out in the order prefetch was told them: this must be the one asked for)
-                const int t0 = ft0 < 0 ? 0 : ft0, t1 = ft1 > len - 1 ? len - 1 : ft1;
-                if (g.b0 != t0 / blkSz || g.b1 != t1 / blkSz || g.r0 != (t0 - R2.d - 2 > 0 ? t0 - R2.d - 2 : 0)) return AUGX_E_ARG;
-            }
-            if (DP->nextWin >= 2) { // (only the blocks of the window before hold anything: a 2 Mbp piece has 250 000 blocks, a window 300)
-                const GatherWin &pw = DP->wins[DP->nextWin - 2];
-                for (int q = pw.b0; q <= pw.b1; q++) R2.blkPool[(size_t)q] = -1;
-            }
-            size_t total = 0;
-            for (int q = g.b0; q <= g.b1; q++) {
-                if (DP->blkCnt[(size_t)q * 2 + 1]) R2.blkPool[(size_t)q] = (int64_t)total;
-                total += DP->blkCnt[(size_t)q * 2 + 1];
-            }
-            R2.pool.assign(DP->poolAll.begin() + g.poolOff, DP->poolAll.begin() + g.poolOff + (int64_t)total);
-            R2.pool.resize(total + 1);
-            if (!fromLists) { R2.F = DP->FAll.data() + g.fOff; R2.fRow0 = g.r0; }
-            R2.fx0 = g.r0;
-            for (int pl = 0; pl < nplP; pl++)
-                for (int rev = 0; rev < 2; rev++) {
-                    std::vector<uint64_t> &dst = rev ? R2.fxR[pl] : R2.fxF[pl];
-                    const uint64_t *src = DP->fxAll.data() + g.fxOff + ((int64_t)pl * 2 + rev) * g.nSlots;
-                    dst.assign(src, src + g.nSlots);
-                }
-            return AUGX_OK;
+            return DP->R.cutWindow(DP->wins, DP->nextWin, ft0, ft1, DP->poolAll, DP->fxAll, DP->FAll, !fromLists);
         };
         return AUGX_OK;
     };
@@ -1699,11 +1704,17 @@ int snippetCacheReplay(augx_decoder *d, augx_batch *b, int64_t &nPatched, bool f
                 if (r0) { int z = 0; rcRun.compare_exchange_strong(z, r0); continue; }
                 std::lock_guard<std::mutex> lk(outMu);
                 for (const MemoPatch &mp : D->R.patches) { pIdx.push_back(mp.item); pTe.push_back(mp.te); }
+                if (d->debugCells) {
+                    for (const MemoPatch &mp : D->R.patches) b->dbgSnip.push_back({todo[k], mp.j, mp.s, mp.eop, mp.te});
+                    b->dbgSnipStats.add(D->R.stats);
+                }
             }
         };
         // (with a matrix to read -- forward algorithm, dense kernels -- a piece whose class steps crowd brings rows x S doubles for most
         //  of its length: 1.1 GB for 2 Mbp at S = 71; fewer of those side by side)
-        const int nW = (int)std::min<size_t>(fromLists ? GROUP : 12, todo.size());
+        //  (never more workers than GROUP: each takes the copy stream of its index, and the decoder has GROUP of them -- with
+        //   AUGX_REPLAY_THREADS below 12 the workers from GROUP on read past the end of the table of streams)
+        const int nW = (int)std::min<size_t>((size_t)(fromLists ? GROUP : std::min(GROUP, 12)), todo.size());
         std::vector<std::thread> th;
         for (int w = 1; w < nW; w++) {
             try { th.emplace_back(worker, w); } catch (const std::system_error &) { break; } // (no more threads to be had: fewer of them)
@@ -1747,6 +1758,7 @@ int utrCachesReplay(augx_decoder *d, augx_batch *b, const double *mat, bool &reb
     int64_t maxList = 0;
     for (int p = 0; p < n; p++)
         if (nPl[p] > 1) { todo.push_back(p); maxList = std::max(maxList, b->hListOffs[(size_t)p + 1] - b->hListOffs[(size_t)p]); }
+    if (d->debugCells) { b->dbgSites.clear(); b->dbgAssStats = AssCounters(); b->dbgTss = 0; }
     if (todo.empty()) { b->memoReplayed = true; return AUGX_OK; }
     AssMemoReplay proto;
     proto.T = &d->hostT;
@@ -1754,7 +1766,7 @@ int utrCachesReplay(augx_decoder *d, augx_batch *b, const double *mat, bool &reb
     MemoReq rq;
     rq.n = proto.nReq;
     for (int r = 0; r < 8; r++) rq.s[r] = r < proto.nReq ? proto.reqS[r] : 0;
-    const int64_t nSiteSlots = W.listCap + 8 * (int64_t)n + 8;
+    const int64_t nSiteSlots = W.listCap + ASS_PAST_END * (int64_t)n + ASS_PAST_END;
     // what the stream's copies and kernels touch, then the guard that waits for them on every way out (declared after it all)
     struct PieceIn { std::vector<int32_t> q; std::vector<uint8_t> alive; std::shared_ptr<AssMemoReplay> Rp; std::vector<AssPatch> pt; std::vector<AssSwIn> sw; int extras = 0; };
     std::vector<std::unique_ptr<PieceIn>> in;
@@ -1772,7 +1784,7 @@ int utrCachesReplay(augx_decoder *d, augx_batch *b, const double *mat, bool &reb
     if (!rc) rc = dChanged.alloc(d, sizeof(int32_t), what);
     if (rc) return rc;
     HIP_TRY(hipMemsetAsync(dChanged.p, 0, sizeof(int32_t), st));
-    const dim3 gridSites((unsigned)((maxList + 8 + 255) / 256), (unsigned)n);
+    const dim3 gridSites((unsigned)((maxList + ASS_PAST_END + 255) / 256), (unsigned)n);
     hipLaunchKernelGGL(kTssReplay, gridSites, dim3(256), 0, st, d->dT, W, mat, dChanged.as<int32_t>());
     hipLaunchKernelGGL(kMemoSites, gridSites, dim3(256), 0, st, d->dT, W, mat, rq, dQ.as<int32_t>(), dAlive.as<uint8_t>());
     hipLaunchKernelGGL(kMemoGates, dim3((unsigned)((W.N + 255) / 256)), dim3(256), 0, st, d->dT, W, rq, dGate.as<uint8_t>());
@@ -1784,7 +1796,7 @@ int utrCachesReplay(augx_decoder *d, augx_batch *b, const double *mat, bool &reb
         in.emplace_back(new PieceIn());
         PieceIn &I = *in.back();
         const int len = b->L.len[p];
-        const int64_t o = b->L.off[p], s0 = b->hListOffs[(size_t)p] + 8 * (int64_t)p, ns = b->hListOffs[(size_t)p + 1] - b->hListOffs[(size_t)p] + 8;
+        const int64_t o = b->L.off[p], s0 = b->hListOffs[(size_t)p] + ASS_PAST_END * (int64_t)p, ns = b->hListOffs[(size_t)p + 1] - b->hListOffs[(size_t)p] + ASS_PAST_END;
         I.Rp = std::make_shared<AssMemoReplay>();
         b->memoOf[(size_t)p] = I.Rp;
         I.q.resize((size_t)ns); I.alive.resize((size_t)ns); I.Rp->gateOwn.resize((size_t)len); I.Rp->planeOwn.resize((size_t)len);
@@ -1808,7 +1820,7 @@ int utrCachesReplay(augx_decoder *d, augx_batch *b, const double *mat, bool &reb
         AssMemoReplay &R = *I.Rp;
         R.T = &d->hostT; R.n = b->L.len[p]; R.plane = R.planeOwn.data(); R.gate = R.gateOwn.data();
         R.requesters();
-        for (int li = 0; li < nList + 8 && li < (int)I.q.size(); li++)
+        for (int li = 0; li < nList + ASS_PAST_END && li < (int)I.q.size(); li++)
             if (I.q[(size_t)li] >= 0) { R.siteQ.push_back(I.q[(size_t)li]); R.siteLi.push_back(li); R.siteAlive.push_back(I.alive[(size_t)li]); }
         R.run();
         I.extras = R.patches(nList, I.pt, I.sw);
@@ -1829,6 +1841,17 @@ int utrCachesReplay(augx_decoder *d, augx_batch *b, const double *mat, bool &reb
         for (AssPatch A : I.pt) { A.swOff += (int32_t)sw.size(); pt.push_back(A); ptPiece.push_back(todo[k]); }
         sw.insert(sw.end(), I.sw.begin(), I.sw.end());
         calls += I.Rp->calls; flushes += I.Rp->flushes; extras += I.extras;
+        if (d->debugCells) {
+            const AssMemoReplay &R = *I.Rp;
+            for (const AssHist &h : R.hist) b->dbgSites.push_back({todo[k], R.siteQ[(size_t)h.site], (int32_t)h.key, -1 - h.pl}); // (the class: below, when the planes' classes are here)
+            b->dbgAssStats.add(R.stats);
+        }
+    }
+    if (d->debugCells && !b->dbgSites.empty()) { // plane -> class
+        std::vector<int32_t> pc((size_t)n * MAXPL);
+        HIP_TRY(hipMemcpyAsync(pc.data(), W.planeCls, sizeof(int32_t) * pc.size(), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        for (auto &r : b->dbgSites) r.cls = pc[(size_t)r.piece * MAXPL + (size_t)(-1 - r.cls)];
     }
     if (!pt.empty()) {
         b->laSwBuf.reset(); W.laSw = nullptr; b->nLaSw = 0; // (the stream is idle)
@@ -1854,6 +1877,7 @@ int utrCachesReplay(augx_decoder *d, augx_batch *b, const double *mat, bool &reb
     }
     HIP_TRY(hipStreamSynchronize(st));
     b->memoReplayed = true;
+    if (d->debugCells) b->dbgTss = nTss;
     if (timing)
         fprintf(stderr, "augx timing:       UTR states, %zu pieces with several GC classes: %d TSS windows and %zu acceptor sites (%zu changes of value during the sweep; %lld past the end of a piece left) rebuilt from "
                         "the reference's caches; inputs gathered in %.3f s, %lld calls of the aSSProb memo walked (emptied %lld times) in %.3f s, values rebuilt in %.3f s\n",

@@ -418,6 +418,7 @@ inline bool modelIsDense(const augx_tables &t) {
     for (int b = 4; b <= 8; b *= 2) { try { checkModelSupported(t, b); return false; } catch (std::exception &) {} }
     try { (void)chooseDenseBlock(t); return true; } catch (std::exception &) { return false; } // (neither: chooseBlockSize reports the trellis kernel's reason)
 }
+constexpr int ASS_PAST_END = 8; // acceptor sites past the end of a piece the memo replay has room for
 // block size of the dense kernels (dense.h): no variable-length or fixed-lag state may read a cell of its own block but through
 // the stage order of densePiece (fixed-lag states, early chains, candidates, late chains, reverse terminal exons)
 inline int chooseDenseBlock(const augx_tables &t) {
@@ -436,6 +437,9 @@ inline int chooseDenseBlock(const augx_tables &t) {
         D.dpc = t.d_polyasig_cleavage; D.boxlen = t.aataaa_boxlen; D.uML = t.utr_max_exon_len; D.uM3S = t.utr_max3single; D.uM3T = t.utr_max3term;
         const int ul = utrMinLag(D);
         if (ul < lag) lag = ul;
+        // (the replay of the aSSProb memo keeps ASS_PAST_END slots per piece for acceptor sites whose longass state would end past the piece:
+        //  there are at most Ae of them -- decoder.hip: kMemoSites, utrCachesReplay)
+        if (t.Ae > ASS_PAST_END) throw std::runtime_error("augx: ass_end too large for the replay of the acceptor-site memo");
         if (t.tss_upwin + 2 > KEY_BIAS || t.aataaa_boxlen + t.d_polyasig_cleavage + 2 > KEY_BIAS) throw std::runtime_error("augx: UTR signal windows too long for the candidate keys");
     }
     int nChain = 0, nFix = 0, nUv = 0;

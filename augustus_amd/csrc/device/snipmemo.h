@@ -14,6 +14,7 @@
 // What comes out are the forward values of the reference to 1e-9, hence its sampled paths.
 #pragma once
 #include <cstdint>
+#include <cstring>
 #include <functional>
 #include <map>
 #include <vector>
@@ -27,7 +28,49 @@ namespace dev {
 struct MemoChunk { int32_t end, len; int32_t plane; };
 struct MemoEntry { int32_t len; std::vector<MemoChunk> dec; };
 
-struct MemoPatch { uint64_t item; double te; }; // global index of the candidate record (as in blkOff)
+// global index of the candidate record (as in blkOff) and its new term; the request it answers, relative to the piece: end base j,
+// short-intron state s, predecessor end eop (tests compare rebuilt terms by this key: candidate space is handed out by atomic adds,
+// so that a global index means nothing outside the run it comes from)
+struct MemoPatch { uint64_t item; double te; int32_t j, s, eop; };
+
+// which of its paths a replay took (plain adds, always compiled; tests/test_emu_replay.py proves that the test inputs reach them)
+enum SnipCount {
+    SC_WINDOWS, SC_MERGED, SC_MERGED_3STEPS, SC_CLAMP_START, SC_CLAMP_END, SC_MAX_BLOCKS /* a maximum */, SC_EMPTY_BLOCK_WINS, SC_PIECES_3WIN,
+    SC_GET_EMPTY, SC_GET_EXTEND, SC_GET_HIT, SC_GET_NONE, SC_GET_PART,
+    SC_ADD_SAME, SC_MAP_FALLBACK, SC_COL0_REQ, SC_BELOW_ROW0, SC_MIXED_SAME, SC_PATCH_FWD, SC_PATCH_REV, SC_WINS_3PLANES, SC_N
+};
+struct SnipCounters {
+    long long c[SC_N] = {0};
+    void add(const SnipCounters &o) { for (int i = 0; i < SC_N; i++) { if (i == SC_MAX_BLOCKS) c[i] = c[i] > o.c[i] ? c[i] : o.c[i]; else c[i] += o.c[i]; } }
+};
+
+// One window of a piece as the windowed mode fetches it: what kGatherWindows (decoder.hip) packs and where.  The window replays the
+// bases t0..t1 (clamped to the piece); it reads the candidate records of the blocks b0..b1 (pool, from poolOff), the prefix slots
+// g0 .. g0 + nSlots - 1 of every plane and strand (from fxOff, laid out [plane][strand][slot]) and the rows r0 .. r0 + nRows - 1 of
+// the matrix (from fOff; none after a Viterbi run of the 47-state kernels, which keep no matrix).  r0 lies d + 2 before t0: a short
+// intron that ends in the window begins at most d bases before it.
+struct GatherWin { int64_t o, gb0, poolOff, fxOff, fOff; int32_t b0, b1, g0, nSlots, nPl, r0, nRows, pad; };
+// the windows {t0, t1} of a piece of `len` bases (as run() hands them to prefetch) -> their GatherWin records; pool / fx / fr: the sizes of
+// the three packed arrays (records, slots, doubles).  blkCnt: [nBlocks][2] of the piece; matrix: rows of a matrix are read
+inline void planGatherWins(const std::vector<std::pair<int, int>> &tt, int len, int blk, int d, int nPl, const uint32_t *blkCnt, bool matrix, int S,
+                           int64_t o, int64_t gb0, std::vector<GatherWin> &wins, int64_t &pool, int64_t &fx, int64_t &fr) {
+    wins.clear();
+    pool = 0; fx = 0; fr = 0;
+    for (auto w : tt) {
+        const int t0 = w.first < 0 ? 0 : w.first, t1 = w.second > len - 1 ? len - 1 : w.second;
+        GatherWin g;
+        memset(&g, 0, sizeof g);
+        g.o = o; g.gb0 = gb0; g.b0 = t0 / blk; g.b1 = t1 / blk;
+        g.r0 = t0 - d - 2 > 0 ? t0 - d - 2 : 0;
+        g.g0 = g.r0; g.nSlots = t1 + 1 - g.r0 + 1; g.nPl = nPl;
+        g.nRows = matrix ? t1 - g.r0 + 1 : 0;
+        g.poolOff = pool; g.fxOff = fx; g.fOff = fr;
+        for (int q = g.b0; q <= g.b1; q++) pool += blkCnt[(size_t)q * 2 + 1];
+        fx += (int64_t)g.nPl * 2 * g.nSlots;
+        fr += (int64_t)g.nRows * S;
+        wins.push_back(g);
+    }
+}
 
 // everything of one piece the replay reads (host memory)
 struct SnippetReplay {
@@ -61,11 +104,46 @@ struct SnippetReplay {
     // fixed-point content prefix of the intron model: fx(plane, rev, g) with g = slot relative to the piece (0 = before the first base)
     std::vector<std::vector<uint64_t>> fxF, fxR; // [plane][n + 1]
     std::vector<MemoPatch> patches;
+    SnipCounters stats;
 
     int64_t segFx(int pl, bool rev, int l, int r) const { // fixed-point content of bases l..r under plane pl
         if (l > r) return 0;
         const std::vector<uint64_t> &a = rev ? fxR[pl] : fxF[pl];
         return (int64_t)(a[(size_t)(r + 1 - fx0)] - a[(size_t)(l - fx0)]);
+    }
+
+    // Windowed mode: the part of the packed arrays (planGatherWins; poolAll / fxAll / FAll: as kGatherWindows left them) that the next
+    // window reads becomes pool / blkPool, fxF / fxR and F.  The windows are handed out in the order prefetch was told them: (ft0, ft1)
+    // must be the one whose turn it is.  blkPool holds [nBlocks] entries, -1 before the first window; only the blocks of the window
+    // before hold anything (a 2 Mbp piece has 250 000 blocks, a window 300).  Returns AUGX_OK, or AUGX_E_ARG for another window.
+    int cutWindow(const std::vector<GatherWin> &wins, size_t &nextWin, int ft0, int ft1, const std::vector<Item> &poolAll,
+                  const std::vector<uint64_t> &fxAll, const std::vector<double> &FAll, bool matrix) {
+        if (nextWin >= wins.size()) return AUGX_E_ARG;
+        const GatherWin &g = wins[nextWin++];
+        {
+            const int t0 = ft0 < 0 ? 0 : ft0, t1 = ft1 > n - 1 ? n - 1 : ft1;
+            if (g.b0 != t0 / blk || g.b1 != t1 / blk || g.r0 != (t0 - d - 2 > 0 ? t0 - d - 2 : 0)) return AUGX_E_ARG;
+        }
+        if (nextWin >= 2) {
+            const GatherWin &pw = wins[nextWin - 2];
+            for (int q = pw.b0; q <= pw.b1; q++) blkPool[(size_t)q] = -1;
+        }
+        size_t total = 0;
+        for (int q = g.b0; q <= g.b1; q++) {
+            if (blkCnt[(size_t)q * 2 + 1]) blkPool[(size_t)q] = (int64_t)total;
+            total += blkCnt[(size_t)q * 2 + 1];
+        }
+        pool.assign(poolAll.begin() + g.poolOff, poolAll.begin() + g.poolOff + (int64_t)total);
+        pool.resize(total + 1);
+        if (matrix) { F = FAll.data() + g.fOff; fRow0 = g.r0; }
+        fx0 = g.r0;
+        for (int pl = 0; pl < g.nPl; pl++)
+            for (int rev = 0; rev < 2; rev++) {
+                std::vector<uint64_t> &dst = rev ? fxR[pl] : fxF[pl];
+                const uint64_t *src = fxAll.data() + g.fxOff + ((int64_t)pl * 2 + rev) * g.nSlots;
+                dst.assign(src, src + g.nSlots);
+            }
+        return AUGX_OK;
     }
 
     // ---- the cache of one strand: lists[base] sorted by length (SnippetList).  The bases a window touches lie in [flatLo, flatLo + size):
@@ -76,6 +154,7 @@ struct SnippetReplay {
     std::vector<MemoEntry> *listAt(int st, int base, bool create) {
         const int64_t k = (int64_t)base - flatLo;
         if (k >= 0 && k < (int64_t)flat[st].size()) return &flat[st][(size_t)k];
+        stats.c[SC_MAP_FALLBACK]++;
         if (create) return &lists[st][base];
         auto f = lists[st].find(base);
         return f == lists[st].end() ? nullptr : &f->second;
@@ -85,7 +164,7 @@ struct SnippetReplay {
         std::vector<MemoEntry> &v = *listAt(st, base, true);
         size_t pos = 0;
         while (pos < v.size() && v[pos].len < len) pos++;
-        if (pos < v.size() && v[pos].len == len) return; // ("tried to add snippet of same length": the reference keeps the old one)
+        if (pos < v.size() && v[pos].len == len) { stats.c[SC_ADD_SAME]++; return; } // ("tried to add snippet of same length": the reference keeps the old one)
         v.insert(v.begin() + (long)pos, MemoEntry{len, dec});
     }
     std::vector<MemoChunk> get(int st, int base, int len, int curPlane) { // SnippetProbs::getSeqProb, src/statemodel.cc:312-342
@@ -95,6 +174,7 @@ struct SnippetReplay {
         if (fv && !fv->empty()) {
             std::vector<MemoEntry> &v = *fv;
             if (v.back().len < len) {
+                stats.c[SC_GET_EXTEND]++;
                 const int l1 = v.back().len;
                 const std::vector<MemoChunk> last = v.back().dec; // (copy: the recursion may add to other lists, not to this one)
                 dec = get(st, base - l1, len - l1, curPlane);
@@ -110,17 +190,20 @@ struct SnippetReplay {
                     partlen = v[k].len;
                     pd = &v[k].dec;
                 }
-                if (partlen == len) dec = *pd;
+                if (partlen == len) { stats.c[SC_GET_HIT]++; dec = *pd; }
                 else if (partlen == 0) {
+                    stats.c[SC_GET_NONE]++;
                     dec.push_back({base, len, curPlane});
                     add(st, base, len, dec);
                 } else {
+                    stats.c[SC_GET_PART]++;
                     const std::vector<MemoChunk> part = *pd;
                     dec = get(st, base - partlen, len - partlen, curPlane);
                     dec.insert(dec.end(), part.begin(), part.end());
                 }
             }
         } else {
+            stats.c[SC_GET_EMPTY]++;
             dec.push_back({base, len, curPlane});
             add(st, base, len, dec);
         }
@@ -140,6 +223,22 @@ struct SnippetReplay {
             else if (t->state_kind[s] == AUGX_K_RLESSD) lessR.push_back(s);
         }
         struct Req { int eop; Item *item; uint64_t gidx; };
+        {   // (what the window is, for the counters)
+            const int c1 = t1 < n - 1 ? t1 : n - 1;
+            stats.c[SC_WINDOWS]++;
+            if (t0 < 0) stats.c[SC_CLAMP_START]++;
+            if (t1 > n - 1) stats.c[SC_CLAMP_END]++;
+            const int nb = c1 / blk - (t0 < 0 ? 0 : t0) / blk + 1;
+            if (nb > stats.c[SC_MAX_BLOCKS]) stats.c[SC_MAX_BLOCKS] = nb;
+            bool emptyBlock = false;
+            for (int q = (t0 < 0 ? 0 : t0) / blk; q <= c1 / blk; q++) emptyBlock = emptyBlock || blkCnt[(size_t)q * 2 + 1] == 0;
+            if (emptyBlock) stats.c[SC_EMPTY_BLOCK_WINS]++;
+            unsigned seen = 0;
+            for (int q = t0 - d - 2 > 0 ? t0 - d - 2 : 0; q <= c1; q++) seen |= 1u << plane[q];
+            int np = 0;
+            for (; seen; seen &= seen - 1) np++;
+            if (np >= 3) stats.c[SC_WINS_3PLANES]++;
+        }
         std::vector<Req> reqs;
         // the candidates of a block, ordered by their (base, state) pair once per block (round 6: every one of the block's 8 x 6
         // (base, short-intron state) pairs went through all of the block's ~120 records)
@@ -174,6 +273,8 @@ struct SnippetReplay {
                         const uint32_t tag = dense ? (eop <= 0 ? SRC_COL0 : SRC_LIST) : I.src >> 30;
                         // (a request is made only where a predecessor cell is alive; column 0 holds the initial probabilities)
                         double pv;
+                        if (tag == SRC_COL0) stats.c[SC_COL0_REQ]++;
+                        else if (fetch && (dense || F) && eop < fRow0) stats.c[SC_BELOW_ROW0]++;
                         if (dense) pv = eop <= 0 ? (F0 ? F0 : F)[(size_t)(I.src & 127u)] : (eop >= fRow0 ? F[(size_t)(eop - fRow0) * S2 + (I.src & 127u)] : -INFINITY);
                         else if (F) pv = tag == SRC_COL0 ? (F0 ? F0 : F)[(size_t)(I.src & 0x3Fu)] : (eop >= fRow0 ? F[(size_t)(eop - fRow0) * S2 + a] : -INFINITY);
                         else if (tag == SRC_COL0) pv = col0[I.src & 0x3Fu];
@@ -201,7 +302,8 @@ struct SnippetReplay {
                         const int cls = planeCls[pl];
                         const double tr = t->ln_trans[((int64_t)cls * S2 + a) * S2 + s];
                         const double te = tr + (t->len_intron[intronLength] + (double)fx * AUGX_FX_INV);
-                        if (te != rq.item->te) { rq.item->te = te; patches.push_back({rq.gidx, te}); }
+                        if (te != rq.item->te) { rq.item->te = te; patches.push_back({rq.gidx, te, j, s, rq.eop}); stats.c[fwd ? SC_PATCH_FWD : SC_PATCH_REV]++; }
+                        else stats.c[SC_MIXED_SAME]++;
                     }
                 }
             }
@@ -212,6 +314,7 @@ struct SnippetReplay {
     // matter then were started no earlier than b - d
     int run() {
         patches.clear();
+        stats = SnipCounters(); // (as AssMemoReplay::run: the counts of this run alone)
         if (nPlanes <= 1) return 0;
         std::vector<int> steps;
         for (int j = 1; j < n; j++)
@@ -223,8 +326,11 @@ struct SnippetReplay {
             size_t k = i + 1;
             while (k < steps.size() && steps[k] - d - 64 <= t1) { t1 = steps[k] + 2 * d + 64; k++; }
             wins.push_back({first, t1});
+            if (k - i >= 2) stats.c[SC_MERGED]++;
+            if (k - i >= 3) stats.c[SC_MERGED_3STEPS]++;
             i = k;
         }
+        if (wins.size() >= 3) stats.c[SC_PIECES_3WIN]++;
         if (prefetch) {
             std::vector<std::pair<int, int>> tt;
             for (auto &w : wins) tt.push_back({w.first - d - 64, w.second});

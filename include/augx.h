@@ -334,6 +334,20 @@ int augx_batch_cells(augx_decoder *d, augx_batch *b, int piece, double *out);
 enum { AUGX_PREP_CODE = 0, AUGX_PREP_CNT, AUGX_PREP_NSM, AUGX_PREP_GCRAW, AUGX_PREP_GCPLANE, AUGX_PREP_FX, AUGX_PREP_SIG, AUGX_PREP_GATE,
        AUGX_PREP_PLSR, AUGX_PREP_UFX, AUGX_PREP_UCNT, AUGX_PREP_CLS, AUGX_PREP_NPLANES, AUGX_PREP_PLANECLS, AUGX_PREP_LISTCNT, AUGX_PREP_N };
 int augx_batch_prep(augx_decoder *d, augx_batch *b, int piece, int which, int plane, void *out, int64_t cap_bytes, int64_t *n_bytes);
+/* test hooks: what the replays of the reference's call-history caches (pieces with several GC classes) did in the last
+ * augx_batch_decode or augx_batch_forward of the batch.  Only valid on a decoder created with AUGX_DEBUG_CELLS=1 (another decoder keeps
+ * nothing); no kernel is launched, nothing is changed.
+ *   counters: the paths the replays took, in the order of SnipCount (device/snipmemo.h) and AssCount (device/assmemo.h), and the forward
+ *     TSS windows whose value changed; returns 100 * (snippet counters) + (memo counters), or AUGX_E_ARG.  The memo counters of what
+ *     happens after the sweep (AC_LATE_CALLS, AC_LATE_FLUSHES, AC_VIT_DIFFS) are always 0 here: augx_batch_sample works on a copy of
+ *     the memo of its own, which the batch does not see -- they say nothing about whether a piece was sampled
+ *   patches: every candidate term rebuilt from the SnippetProbs cache: (piece, end base j, state, predecessor end eop) and the term
+ *   sites: every change of the value of a forward acceptor site in the aSSProb memo, in the order of the calls of its piece: (piece, end q
+ *     of the site's longass state, (asking column << 7) | asking state, GC class the value is computed with)
+ * patches / sites return the number of records and copy at most cap of them (the arrays may be NULL with cap = 0), or AUGX_E_ARG */
+int augx_batch_replay_counters(augx_decoder *d, augx_batch *b, long long *snip, long long *ass, long long *tss_changed);
+int64_t augx_batch_replay_patches(augx_decoder *d, augx_batch *b, int32_t *keys /* [cap][4] */, double *te /* [cap] */, int64_t cap);
+int64_t augx_batch_replay_sites(augx_decoder *d, augx_batch *b, int32_t *recs /* [cap][4] */, int64_t cap);
 /* forward algorithm of a decoded batch (reference NAMGene::viterbiAndForward with needForwardTable, src/namgene.cc:168-365,
  * the per-state `fwdsum`s): the dense ln F matrix stays on the device for the posterior sampling; the second call copies the
  * len*S matrix of one piece (-inf = absent) and ln P(sequence) to the host (tests; the executable's --sample > 0 goes through

@@ -43,6 +43,20 @@
 namespace {
 
 int g_snippetCache = 1; // twin_set_snippet_cache
+// Test aid, off by default (twin_set_cache_log): what the two restated caches did in the last twin_decode, value by value.  The decode
+// itself does not read it.
+//  - every request of a short-intron state (end base j, state s, predecessor end eop) that the cache answered with another content
+//    than the tables of the class of j give, with the term the trellis then adds to the predecessor value:
+//    lnT(c, anc[s][0], s) + (len_intron + content).  A term of -inf is no candidate and is left out.
+//  - every computation of a forward acceptor-site value into the aSSProb memo: the site by the end q of its longass state
+//    (not clamped to the piece), the column and state that asked, the class the value was computed with
+//  - how often the memo was emptied
+struct SnipLogRec { int32_t j, s, eop, pad; double te; };
+struct SiteLogRec { int32_t q, j, s, cls; };
+int g_cacheLog = 0;
+std::vector<SnipLogRec> g_snipLog;
+std::vector<SiteLogRec> g_siteLog;
+long long g_memoFlushLog = 0;
 // Entry 0 of the reference's tssProbsPlus / tssProbsMinus lives on from sequence to sequence while the sequences keep one length: it is
 // neither cleared at a class step (updateToLocalGC clears [from, to) with from = 1, src/utrmodel.cc:779-781) nor re-allocated
 // (initAlgorithms, :744-747).  twin_set_tss0_carry(1): consecutive twin_decode calls are the reference's consecutive sequences
@@ -698,6 +712,8 @@ struct Twin {
                 double restSeq = useSnips ? (double)snipGet(fwd ? 0 : 1, j, j - begin + 1, c) * AUGX_FX_INV
                                           : (fwd ? seg(A.inF, begin, j) : seg(A.inR, begin, j));
                 double emi = t.len_intron[intronLength] + restSeq;
+                if (g_cacheLog && useSnips && emi > NINF && restSeq != (fwd ? seg(A.inF, begin, j) : seg(A.inR, begin, j)))
+                    g_snipLog.push_back({j, s, eop, 0, lnT(c, t.anc[s][0], s) + emi});
                 if (emi == NINF) continue;
                 for (int ai = 0; ai < t.n_anc[s]; ai++) {
                     int a = t.anc[s][ai];
@@ -922,6 +938,7 @@ struct Twin {
     // With the caches off (twin_set_snippet_cache(0): the first pass of the device): the class of the base the longass state ends at.
     std::map<int, int> memoF;
     bool useMemo = false;
+    int curJ = 0, curS = 0; // (the cell the sweep is at: who asks)
     long long memoFlushes = 0, memoForeign = 0; // (test aid: times the memo was emptied; answers that came from another class than the natural one)
     int assMemoClass(int base) {
         int q = base + t.U + t.As + 2 + t.Ae - 1;
@@ -933,6 +950,7 @@ struct Twin {
         if (it != memoF.end()) { if (it->second != cls[q]) memoForeign++; return it->second; }
         if (!possASS(base + t.U + t.As + 1)) return curCls; // (no acceptor site: the value is 0, nothing is kept, :1140-1143)
         memoF[base] = curCls;
+        if (g_cacheLog) g_siteLog.push_back({base + t.U + t.As + 2 + t.Ae - 1, curJ, curS, curCls});
         if (curCls != cls[q]) memoForeign++;
         return curCls;
     }
@@ -1176,6 +1194,7 @@ struct Twin {
                 for (int s = 0; s < S; s++) {
                     if (!t.reachable[s]) continue;
                     int kind = t.state_kind[s];
+                    curJ = j; curS = s;
                     if (kind == AUGX_K_IGENIC) igenicCell(s, j);
                     else if (kind <= AUGX_K_RTERMINAL) exonCell(s, j);
                     else if (kind <= AUGX_K_RLONGASS) intronCell(s, j);
@@ -1239,6 +1258,17 @@ double twin_utr_forward_cell(const augx_tables *t, const char *seq, int64_t len,
 }
 /* 1 (default): short-intron interiors through the restated SnippetProbs cache, as the reference; 0: class of the end base */
 void twin_set_snippet_cache(int on) { g_snippetCache = on; }
+/* the log of the two caches (above): on / off; the getters return the number of records of the last twin_decode and copy at most cap */
+void twin_set_cache_log(int on) { g_cacheLog = on; g_snipLog.clear(); g_siteLog.clear(); g_memoFlushLog = 0; }
+int64_t twin_snippet_log(int32_t *keys /* [cap][3]: j, s, eop */, double *te, int64_t cap) {
+    for (int64_t i = 0; i < cap && i < (int64_t)g_snipLog.size(); i++) { keys[i * 3] = g_snipLog[i].j; keys[i * 3 + 1] = g_snipLog[i].s; keys[i * 3 + 2] = g_snipLog[i].eop; te[i] = g_snipLog[i].te; }
+    return (int64_t)g_snipLog.size();
+}
+int64_t twin_site_log(int32_t *recs /* [cap][4]: q, asking column, asking state, class */, int64_t cap) {
+    for (int64_t i = 0; i < cap && i < (int64_t)g_siteLog.size(); i++) { recs[i * 4] = g_siteLog[i].q; recs[i * 4 + 1] = g_siteLog[i].j; recs[i * 4 + 2] = g_siteLog[i].s; recs[i * 4 + 3] = g_siteLog[i].cls; }
+    return (int64_t)g_siteLog.size();
+}
+long long twin_memo_flushes() { return g_memoFlushLog; }
 void twin_set_tss0_carry(int on) { g_tss0Carry = on; g_tss0Size = -1; g_tss0Set[0] = g_tss0Set[1] = 0; }
 /* decode one piece on the CPU.  V_out (len*S doubles) and gc_out (len int32) may be NULL.
  * states_out receives at most cap records; *n_states is the number available. */
@@ -1248,7 +1278,9 @@ int twin_decode(const augx_tables *t, const char *seq, int64_t len, int init_kin
     Twin tw(*t, seq, (int)len);
     std::vector<augx_state> path;
     double lnv;
+    if (g_cacheLog) { g_snipLog.clear(); g_siteLog.clear(); }
     int rc = tw.run(init_kind, term_kind, &lnv, path);
+    if (g_cacheLog) g_memoFlushLog = tw.memoFlushes;
     if (ln_viterbi) *ln_viterbi = lnv;
     if (V_out) memcpy(V_out, tw.V.data(), sizeof(double) * (size_t)len * t->S);
     if (gc_out) for (int64_t i = 0; i < len; i++) gc_out[i] = tw.cls[i];

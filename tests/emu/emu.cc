@@ -11,6 +11,8 @@
 #include <cstdlib>
 #include <chrono>
 #include <vector>
+#include <memory>
+#include <functional>
 #include "../../augustus_amd/csrc/device/kernels.h"
 #include "../../augustus_amd/csrc/device/dense.h"
 #include "../../augustus_amd/csrc/device/assmemo.h"
@@ -85,6 +87,73 @@ static int g_nsamples = 0;
 static std::vector<double> g_tss0; // emu_set_tss0: [n][2] for the next emu_decode (BatchView::tss0), empty: none
 static augx_rand *g_rand = nullptr;
 static std::vector<std::vector<std::vector<augx_state>>> g_samples;
+
+// ---- what the replays of the reference's caches (snipmemo.h, assmemo.h) did in the last emu_decode, for tests/test_emu_replay.py:
+//      the rebuilt candidate terms by their key, the history of the acceptor sites, the counters of both replays
+namespace {
+struct EmuSnipRec { int32_t piece, j, s, eop; double te; };
+struct EmuSiteRec { int32_t piece, q, key, cls; };
+std::vector<EmuSnipRec> g_snipRecs;
+std::vector<EmuSiteRec> g_siteRecs;
+SnipCounters g_snipStats;
+AssCounters g_assStats;
+long long g_tssChanged = 0;
+int g_replayRc = 0;
+void replayLogReset() { g_replayRc = 0; g_snipRecs.clear(); g_siteRecs.clear(); g_snipStats = SnipCounters(); g_assStats = AssCounters(); g_tssChanged = 0; }
+
+// Windowed mode (AUGX_EMU_WINDOWED=1): the route of the device library -- the plan of the windows and the cut of one window out of
+// the packed arrays are the library's own host functions (snipmemo.h: planGatherWins, cutWindow); what kGatherWindows packs is
+// restated by a plain loop: the records of the blocks in block order with a running offset, the prefix slots [plane][strand][slot]
+// from g0, the rows of the matrix from r0.  The rebuilt terms go back into the candidate records afterwards, as kPatchItems writes them.
+// (mat: the matrix that tells which cells are alive, or null after a Viterbi run of the 47-state kernels)
+struct EmuWin { std::vector<GatherWin> wins; std::vector<Item> poolAll; std::vector<uint64_t> fxAll; std::vector<double> FAll; size_t nextWin = 0; };
+void replayWindowed(SnippetReplay &R, const BatchView &B, int64_t o, const double *mat, std::shared_ptr<EmuWin> W) {
+    const int len = R.n, S = R.S, blk = R.blk;
+    const int64_t gb0 = o / blk;
+    const int nBlocks = (len + blk - 1) / blk;
+    const bool matrix = mat != nullptr;
+    R.F = nullptr; R.F0 = matrix ? mat + (o + 1) * S : nullptr;
+    R.items = nullptr; R.item0 = 0;
+    R.blkPool.assign((size_t)nBlocks, -1);
+    R.fxF.assign((size_t)R.nPlanes, {}); R.fxR.assign((size_t)R.nPlanes, {});
+    SnippetReplay *Rp = &R;
+    const BatchView *Bp = &B;
+    R.prefetch = [=](const std::vector<std::pair<int, int>> &tt) -> int {
+        int64_t pool = 0, fx = 0, fr = 0;
+        W->nextWin = 0;
+        planGatherWins(tt, len, blk, Rp->d, Rp->nPlanes, Rp->blkCnt, matrix, S, o, gb0, W->wins, pool, fx, fr);
+        W->poolAll.assign((size_t)pool + 1, Item()); W->fxAll.assign((size_t)fx + 1, 0); W->FAll.assign((size_t)fr + 1, 0.0);
+        for (const GatherWin &w : W->wins) {
+            uint64_t running = 0;
+            for (int q = w.b0; q <= w.b1; q++) {
+                const uint32_t cnt = Bp->blkCnt[(w.gb0 + q) * 2 + 1];
+                const Item *src = Bp->items + Bp->blkOff[(w.gb0 + q) * 2 + 1];
+                for (uint32_t i = 0; i < cnt; i++) W->poolAll.at((size_t)(w.poolOff + running + i)) = src[i];
+                running += cnt;
+            }
+            for (int pl = 0; pl < w.nPl; pl++)
+                for (int rev = 0; rev < 2; rev++)
+                    for (int k = 0; k < w.nSlots; k++)
+                        W->fxAll.at((size_t)(w.fxOff + ((int64_t)pl * 2 + rev) * w.nSlots + k)) = Bp->fx[(int64_t)pl * Bp->N * NFX + fidx(w.o + w.g0 + k, rev ? FX_INR : FX_INF, NFX)];
+            if (matrix)
+                for (int64_t i = 0; i < (int64_t)w.nRows * S; i++) W->FAll.at((size_t)(w.fOff + i)) = mat[(w.o + 1 + w.r0) * S + i];
+        }
+        return AUGX_OK;
+    };
+    R.fetch = [=](int ft0, int ft1) -> int { return Rp->cutWindow(W->wins, W->nextWin, ft0, ft1, W->poolAll, W->fxAll, W->FAll, matrix); };
+}
+// run the replay of piece p (whole mode: R as the caller set it up), keep what it did
+int replayRun(SnippetReplay &R, BatchView &B, int p, int64_t o, const double *mat) {
+    const bool windowed = getenv("AUGX_EMU_WINDOWED") && atoi(getenv("AUGX_EMU_WINDOWED")) != 0;
+    if (windowed) replayWindowed(R, B, o, mat, std::make_shared<EmuWin>());
+    const int rc = R.run();
+    if (rc) { fprintf(stderr, "emu: the replay of piece %d failed (%d)\n", p, rc); g_replayRc = rc; } // (emu_decode hands it on)
+    if (windowed) for (const MemoPatch &mp : R.patches) B.items[mp.item].te = mp.te;
+    for (const MemoPatch &mp : R.patches) g_snipRecs.push_back({p, mp.j, mp.s, mp.eop, mp.te});
+    g_snipStats.add(R.stats);
+    return rc;
+}
+} // namespace
 
 // ---- models decoded by the dense kernels (device/dense.h: the 71-state model with UTR states): the same prep kernels, the UTR
 //      prefix / signal / site-list kernels, the candidate records of kCand in their dense form, densePiece, denseBacktracePiece
@@ -271,7 +340,7 @@ static int emu_decode_dense(const augx_tables *t, const augx_piece *pieces, int 
             const uint64_t *fx = B.fx + (int64_t)pl * B.N * NFX;
             for (int g = 0; g <= len; g++) { R.fxF[pl][g] = fx[fidx(o + g, FX_INF, NFX)]; R.fxR[pl][g] = fx[fidx(o + g, FX_INR, NFX)]; }
         }
-        R.run();
+        replayRun(R, B, p, o, mat);
         if (getenv("AUGX_EMU_STATS")) fprintf(stderr, "emu stats (dense): piece %d: %zu candidate terms rebuilt from the reference's snippet cache\n", p, R.patches.size());
         return !R.patches.empty();
     };
@@ -291,6 +360,7 @@ static int emu_decode_dense(const augx_tables *t, const augx_piece *pieces, int 
         int nTss = 0;
         const int nTf = (int)B.ucnt[fidx(o + len, UCNT_TF, NUCNT)];
         for (int li = 0; li < nTf; li++) nTss += k1TssReplay(T, B, p, li, M);
+        g_tssChanged += nTss;
         memoOf[(size_t)p] = std::make_shared<AssMemoReplay>();
         AssMemoReplay &R = *memoOf[(size_t)p];
         R.T = &T; R.n = len; R.plane = B.gcPlane + o + 1;
@@ -312,6 +382,8 @@ static int emu_decode_dense(const augx_tables *t, const augx_piece *pieces, int 
         laSw.resize(laSwIn.size());
         B.laSw = laSw.data();
         for (const AssPatch &A : pt) k1AssPatch(T, B, p, A, laSwIn.data(), laSw.data());
+        for (const AssHist &h : R.hist) g_siteRecs.push_back({p, R.siteQ[(size_t)h.site], (int32_t)h.key, (B.planeCls + (int64_t)p * MAXPL)[h.pl]});
+        g_assStats.add(R.stats);
         if (getenv("AUGX_EMU_STATS"))
             fprintf(stderr, "emu stats (dense): piece %d: %d TSS windows and %zu acceptor sites (%zu changes of value during the sweep, %d sites past the end left) rebuilt from the reference's caches; aSSProb memo: %lld calls walked, emptied %lld times\n",
                     p, nTss, pt.size(), laSwIn.size() - sw0, extras, R.calls, R.flushes);
@@ -391,6 +463,7 @@ static int emu_decode_dense(const augx_tables *t, const augx_piece *pieces, int 
             samplePaths(P, g_nsamples, *g_rand, g_samples[p], sst);
             if (getenv("AUGX_EMU_STATS")) fprintf(stderr, "emu sampler: piece %d (%d bases): stops %.3f s, %d paths drawn in %.3f s (the generator's buffers so far: %.3f s)\n", p, P.n, std::chrono::duration<double>(ts1 - ts0).count(), g_nsamples,
                                                   std::chrono::duration<double>(std::chrono::steady_clock::now() - ts1).count(), g_rand->refillSeconds);
+            if (P.memo) { g_assStats.c[AC_LATE_CALLS] += P.memo->stats.c[AC_LATE_CALLS]; g_assStats.c[AC_LATE_FLUSHES] += P.memo->stats.c[AC_LATE_FLUSHES]; g_assStats.c[AC_VIT_DIFFS] += P.memoVitDiffs; }
             if (getenv("AUGX_EMU_STATS") && P.memo) fprintf(stderr, "emu sampler: piece %d: aSSProb memo carried on: %lld calls in all, emptied %lld times; candidates of the Viterbi path's UTR exon steps the back-tracking values under another class: %ld\n",
                                                             p, P.memo->calls, P.memo->flushes, P.memoVitDiffs);
         }
@@ -418,7 +491,7 @@ static int emu_decode_dense(const augx_tables *t, const augx_piece *pieces, int 
     }
     free(B.items);
     for (void *p : bufs) free(p);
-    return 0;
+    return g_replayRc;
 }
 
 extern "C" {
@@ -509,6 +582,29 @@ int emu_prep(int p, int which, int plane, void *out, int64_t cap_bytes, int64_t 
 }
 int emu_near_ties(int p) { return p >= 0 && p < (int)g_nearTies.size() ? g_nearTies[p] : -1; }
 // values of the TSS window at base 0 of the pieces of the NEXT emu_decode, [n][2] forward / reverse, NaN: the piece's own (n = 0: none)
+void emu_ass_past_end(const augx_tables *t, int *out) { out[0] = t->Ae; out[1] = ASS_PAST_END; out[2] = t->utr ? 1 : 0; } // (layout.h: chooseDenseBlock refuses Ae > ASS_PAST_END)
+// block size of the dense kernels for the model with another ass_end (a copy of the tables: the model is not touched); -2: refused for
+// its ass_end, -1: refused for another reason
+int emu_dense_block_with_ass_end(const augx_tables *t, int ae) {
+    augx_tables c = *t;
+    c.Ae = ae;
+    try { return chooseDenseBlock(c); } catch (std::exception &e) { return strstr(e.what(), "ass_end") ? -2 : -1; }
+}
+// the replays of the reference's caches in the last emu_decode (above).  The getters return the number of records and copy at most cap
+int emu_replay_counters(long long *snip, long long *ass, long long *tss) {
+    for (int i = 0; i < SC_N; i++) snip[i] = g_snipStats.c[i];
+    for (int i = 0; i < AC_N; i++) ass[i] = g_assStats.c[i];
+    *tss = g_tssChanged;
+    return SC_N * 100 + AC_N;
+}
+int64_t emu_replay_patches(int32_t *keys /* [cap][4]: piece, j, s, eop */, double *te, int64_t cap) {
+    for (int64_t i = 0; i < cap && i < (int64_t)g_snipRecs.size(); i++) { const EmuSnipRec &r = g_snipRecs[(size_t)i]; keys[i * 4] = r.piece; keys[i * 4 + 1] = r.j; keys[i * 4 + 2] = r.s; keys[i * 4 + 3] = r.eop; te[i] = r.te; }
+    return (int64_t)g_snipRecs.size();
+}
+int64_t emu_replay_sites(int32_t *recs /* [cap][4]: piece, q, key, class */, int64_t cap) {
+    for (int64_t i = 0; i < cap && i < (int64_t)g_siteRecs.size(); i++) { const EmuSiteRec &r = g_siteRecs[(size_t)i]; recs[i * 4] = r.piece; recs[i * 4 + 1] = r.q; recs[i * 4 + 2] = r.key; recs[i * 4 + 3] = r.cls; }
+    return (int64_t)g_siteRecs.size();
+}
 void emu_set_tss0(const double *v, int n) { g_tss0.assign(v, v + (v ? 2 * (size_t)n : 0)); }
 void emu_set_sampling(int n, unsigned seed) {
     g_nsamples = n;
@@ -561,6 +657,7 @@ int emu_sample_get(int p, int it, int32_t *out, int cap) {
 // fwd_out (optional): the dense ln F matrices of the forward algorithm, piece after piece; lnfwd_out[n]: ln P(sequence)
 int emu_decode(const augx_tables *t, const augx_piece *pieces, int n, double *lnv, int32_t *status, int32_t *path_out,
                int32_t path_cap, int32_t *path_n, double *cells_out, int32_t *cls_out, double *fwd_out, double *lnfwd_out) {
+    replayLogReset();
     if (modelIsDense(*t)) return emu_decode_dense(t, pieces, n, lnv, status, path_out, path_cap, path_n, cells_out, cls_out, fwd_out, lnfwd_out);
     int blk = 8;
     try {
@@ -787,7 +884,7 @@ int emu_decode(const augx_tables *t, const augx_piece *pieces, int n, double *ln
                 for (int g = 0; g <= len; g++) { R.fxF[pl][g] = fx[fidx(o + g, FX_INF, NFX)]; R.fxR[pl][g] = fx[fidx(o + g, FX_INR, NFX)]; }
             }
             const auto tr0 = std::chrono::steady_clock::now();
-            R.run();
+            replayRun(R, B, p, o, nullptr);
             if (getenv("AUGX_EMU_STATS")) fprintf(stderr, "emu stats: piece %d (%d bases): snippet replay %.3f s, %zu terms rebuilt\n", p, len, std::chrono::duration<double>(std::chrono::steady_clock::now() - tr0).count(), R.patches.size());
             nPatched += R.patches.size();
         }
@@ -838,7 +935,7 @@ int emu_decode(const augx_tables *t, const augx_piece *pieces, int n, double *ln
                     const uint64_t *fx = B.fx + (int64_t)pl * B.N * NFX;
                     for (int g = 0; g <= len; g++) { R.fxF[pl][g] = fx[fidx(o + g, FX_INF, NFX)]; R.fxR[pl][g] = fx[fidx(o + g, FX_INR, NFX)]; }
                 }
-                R.run();
+                replayRun(R, B, p, o, B.fwd);
                 if (getenv("AUGX_EMU_STATS")) fprintf(stderr, "emu stats: piece %d: %zu candidate terms rebuilt from the reference's snippet cache\n", p, R.patches.size());
                 if (!R.patches.empty()) fwdPiece(p);
             }
@@ -912,6 +1009,6 @@ int emu_decode(const augx_tables *t, const augx_piece *pieces, int n, double *ln
     free(B.cells); free(B.vig); free(B.longV); free(B.laPos); free(B.laVal); free(B.lrPos); free(B.lrVal); free(B.ldEnt); free(B.ldVal);
     free(B.rdEnt); free(B.rdVal); free(B.atgPos); free(B.pathRec);
     free(B.laPls); free(B.laFx); free(B.lrEt); free(B.lrFx); free(B.atgD); free(B.atgFx); free(B.rsPos); free(B.rsBegin); free(B.rsFx); free(B.plsR); free(B.gcRaw); free(B.gcPlane);
-    return 0;
+    return g_replayRc;
 }
 }

@@ -124,6 +124,43 @@ def twin_decode(tables_ptr, seq, S, cells=False, init_kind=0, term_kind=0, cache
     return rc, lnv.value, path, V, gc
 
 
+def twin_cache_log(tables_ptr, seq, S, cells=False, init_kind=0, term_kind=0):
+    """twin_decode with the restated caches on and their log kept (oracle/ghmm_twin.cc: twin_set_cache_log).  Returns
+    (twin_decode's tuple, {(j, s, eop): term} of every short-intron request the SnippetProbs cache answered with another content than
+    the class of j gives, [(q, asking column, asking state, class)] of every computation of a forward acceptor-site value into the
+    aSSProb memo in the order of the calls, the number of times the memo was emptied)."""
+    T = twin()
+    T.twin_snippet_log.restype = T.twin_site_log.restype = ctypes.c_int64
+    T.twin_memo_flushes.restype = ctypes.c_longlong
+    T.twin_set_cache_log(1)
+    try:
+        res = twin_decode(tables_ptr, seq, S, cells=cells, init_kind=init_kind, term_kind=term_kind, cache=True)
+        n = T.twin_snippet_log(None, None, ctypes.c_int64(0))
+        keys, te = np.zeros((max(n, 1), 3), dtype=np.int32), np.zeros(max(n, 1))
+        T.twin_snippet_log(keys.ctypes.data_as(ctypes.c_void_p), te.ctypes.data_as(ctypes.c_void_p), ctypes.c_int64(n))
+        terms = {}
+        for k, v in zip(keys[:n].tolist(), te[:n].tolist()):
+            assert tuple(k) not in terms, k  # (a request is made once)
+            terms[tuple(k)] = v
+        m = T.twin_site_log(None, ctypes.c_int64(0))
+        sites = np.zeros((max(m, 1), 4), dtype=np.int32)
+        T.twin_site_log(sites.ctypes.data_as(ctypes.c_void_p), ctypes.c_int64(m))
+        return res, terms, [tuple(r) for r in sites[:m].tolist()], int(T.twin_memo_flushes())
+    finally:
+        T.twin_set_cache_log(0)
+
+
+def site_changes(sites):
+    """the log of site computations -> [(q, key, class)] as the replay keeps its history (assmemo.h: hist): a computation that gives a
+    site the class it had before changes no value and is left out; key = (column << 7) | state"""
+    last, out = {}, []
+    for q, j, s, c in sites:
+        if last.get(q) != c:
+            last[q] = c
+            out.append((q, (j << 7) | s, c))
+    return out
+
+
 def ref_harness(fasta, species, extra=(), cells_file=None, cfg=None):
     """The REAL reference through oracle/_ref/ref_harness.  Returns list of dicts per record."""
     env = dict(os.environ, AUGUSTUS_CONFIG_PATH=cfg or config_path())
@@ -1016,3 +1053,167 @@ def dense_backtrace_prefixes(kmax=31):
     lens = [n for n in BACKTRACE_EDGE_LENS if n <= 256 * kmax + 2]
     assert len(src) >= lens[-1]
     return [("softmask_all[:%d]" % n, src[:n]) for n in lens]
+
+
+# paths of the replays of the reference's call-history caches (snipmemo.h: SnipCount; assmemo.h: AssCount), in the order of the counters
+SNIP_COUNTERS = ("windows", "merged", "merged_3steps", "clamp_start", "clamp_end", "max_blocks", "empty_block_wins", "pieces_3win",
+                 "get_empty", "get_extend", "get_hit", "get_none", "get_part", "add_same", "map_fallback", "col0_req", "below_row0",
+                 "mixed_same", "patch_fwd", "patch_rev", "wins_3planes")
+ASS_COUNTERS = ("calls", "flushes", "skips", "skipped_sites", "flush_in_skip", "first_longass", "first_utr5internal", "first_utr5term",
+                "first_utr3internal", "first_utr3term", "long_foreign", "sites_0changes", "sites_1change", "sites_2changes", "extras",
+                "late_calls", "late_flushes", "vit_diffs")
+REPLAY_MAXIMA = ("max_blocks",)  # (a maximum, not a count)
+
+
+def merge_counters(a, b):
+    return {k: (max(a.get(k, 0), v) if k in REPLAY_MAXIMA else a.get(k, 0) + v) for k, v in b.items()}
+
+
+def _replay_out(counters, patches, sites):
+    """(n, snip[], ass[], tss), (keys [n][4], te) and recs [m][4] -> ({counter: value}, {piece: {(j, s, eop): te}}, {piece: [(q, key, class)]})"""
+    code, snip, ass, tss = counters
+    assert code == len(SNIP_COUNTERS) * 100 + len(ASS_COUNTERS), code
+    cnt = dict(zip(SNIP_COUNTERS, snip))
+    cnt.update(zip(ASS_COUNTERS, ass))
+    cnt["tss_changed"] = tss
+    terms, hist = {}, {}
+    for k, v in zip(*patches):
+        d = terms.setdefault(k[0], {})
+        assert tuple(k[1:]) not in d, k  # (a candidate is patched once)
+        d[tuple(k[1:])] = v
+    for r in sites:
+        hist.setdefault(r[0], []).append(tuple(r[1:]))
+    return cnt, terms, hist
+
+
+def _replay_fetch(get_counters, get_patches, get_sites):
+    snip, ass, tss = (ctypes.c_longlong * 64)(), (ctypes.c_longlong * 64)(), ctypes.c_longlong()
+    code = get_counters(snip, ass, ctypes.byref(tss))
+    n = get_patches(None, None, ctypes.c_int64(0))
+    keys, te = np.zeros((max(n, 1), 4), dtype=np.int32), np.zeros(max(n, 1))
+    assert get_patches(keys.ctypes.data_as(ctypes.c_void_p), te.ctypes.data_as(ctypes.c_void_p), ctypes.c_int64(n)) == n
+    m = get_sites(None, ctypes.c_int64(0))
+    recs = np.zeros((max(m, 1), 4), dtype=np.int32)
+    assert get_sites(recs.ctypes.data_as(ctypes.c_void_p), ctypes.c_int64(m)) == m
+    return _replay_out((code, list(snip[:len(SNIP_COUNTERS)]), list(ass[:len(ASS_COUNTERS)]), tss.value),
+                       (keys[:n].tolist(), te[:n].tolist()), recs[:m].tolist())
+
+
+def emu_replay_log(lib=None):
+    """what the cache replays of the last emu_decode did: ({counter: value}, {piece: {(j, s, eop): rebuilt term}},
+    {piece: [(q, key, class)] in the order of the calls})"""
+    E = _emu_of(lib)
+    E.emu_replay_patches.restype = E.emu_replay_sites.restype = ctypes.c_int64
+    return _replay_fetch(E.emu_replay_counters, E.emu_replay_patches, E.emu_replay_sites)
+
+
+def batch_replay_log(batch):
+    """the same from a decoded batch of the device library (augustus_amd.Batch.replay_hooks)"""
+    return _replay_fetch(*batch.replay_hooks())
+
+
+def _two_class_piece(seed, head=1000, mid=5000, tail=1000):
+    """two GC classes under human (measured with the twin): 68 % GC, 36 %, 68 % -- the class steps lie about 1.7 kb from either end"""
+    return _gc_dna(head, 0.68, seed) + _gc_dna(mid, 0.36, seed + 1000) + _gc_dna(tail, 0.68, seed + 2000)
+
+
+def _ag_rich(n, gc, seed, every):
+    """random DNA of the given GC content with an AG about every `every` bases: some 2000 acceptor sites in 9 kb"""
+    rng = random.Random(seed)
+    s = list(_gc_dna(n, gc, seed))
+    i = rng.randrange(every)
+    while i + 1 < n:
+        s[i], s[i + 1] = "A", "G"
+        i += rng.randint(every - 2, every + 2)
+    return "".join(s)
+
+
+# The models of the replay tests.  The class steps of a piece lie between GCwinsize / 2 + 1 and len - GCwinsize / 2 (the stairs hold the
+# class of the first window up to there and of the last window from there; smoothing only removes steps).  A replay window is clamped at
+# the start of its piece for a step below d + 64 and at its end for a step above len - 2 d - 65: with the models' own windows (human
+# 3000 with d = 584, all others 10 000 with d <= 950) no window of any piece is clamped.  GCwinsize is an option of the reference:
+# at 600 (human) the steps come within 301 bases of either end.
+REPLAY_CFGS = {
+    "human": ("human", {"softmasking": "0"}),
+    "human_w600": ("human", {"softmasking": "0", "GCwinsize": "600"}),
+    "nasonia_w1000": ("nasonia", {"UTR": "off", "sample": "0", "softmasking": "0", "GCwinsize": "1000"}),
+    "human_utr": ("human", {"UTR": "on", "softmasking": "0"}),
+    "human_utr_w600": ("human", {"UTR": "on", "softmasking": "0", "GCwinsize": "600"}),
+}
+REPLAY_DENSE = ("human_utr", "human_utr_w600")
+
+
+def replay_batch_pieces(n_multi=13, distinct=None):
+    """[(name, sequence)]: n_multi pieces with two GC classes under human (class steps near 1720 and 5245) and a single-class piece of
+    2 kb after each: more multi-class pieces than the replay of a batch with a matrix has workers (12), at piece indices above 0.
+    distinct: that many different two-class sequences, taken in turn (the oracle decodes a sequence once)"""
+    recs = []
+    for k in range(n_multi):
+        q = k % (distinct or n_multi)
+        recs.append(("two%d" % q, _two_class_piece(5 + q)))
+        recs.append(("one%d" % k, _gc_dna(2000, 0.40, 700 + k)))
+    return recs
+
+
+def replay_edge_cases():
+    """{configuration of REPLAY_CFGS: [(name, sequence, init_kind, term_kind)]}, pieces of at most 12 kb made for the paths of the cache
+    replays (snipmemo.h, assmemo.h) that the other fixtures do not reach; tests/test_emu_replay.py shows from the replays' counters that
+    they do (found by a search on the CPU, driven by those counters):
+    - a class step 474 bases after the piece start, one some 470 before the end (pieces of different lengths: entry 0 of the reference's
+      TSS caches lives on between sequences of one length, tests/test_memo_replay.py), both in one piece (one merged window, clamped on either
+      side), the last also as an interior cut (init_kind = term_kind = 1): the j = 1 start of a window, predecessors in column 0;
+    - nasonia (d = 950, five classes) over a GC gradient: six steps in one window of 862 blocks of 8 bases that reads four planes;
+    - the 13 two-class pieces of replay_batch_pieces among single-class ones, as one batch;
+    - UTR states: 9 kb with an AG every 4 bases and four or five GC stretches -- the aSSProb memo is emptied 19 (ag5) and 20 (ag4) times, also inside the
+      range a requester skips, sites change their value twice, each of the five requester kinds asks first; an AG in the last bases;
+      7.2 kb with an AG every 3 bases (238 flushes): a requester comes back to a range it has walked when the memo is full, and
+      to sites above the one at which its own walk emptied the memo (a walk that skips either is told apart from the call-by-call
+      one by this piece alone)"""
+    ends = [("step_start", _gc_dna(400, 0.70, 1) + _gc_dna(3000, 0.34, 2), 0, 0),
+            ("step_end", _gc_dna(3100, 0.34, 3) + _gc_dna(400, 0.72, 4), 0, 0),
+            ("step_both", _gc_dna(350, 0.72, 5) + _gc_dna(1500, 0.34, 6) + _gc_dna(350, 0.72, 7), 0, 0),
+            ("step_both_cut", _gc_dna(350, 0.72, 5) + _gc_dna(1500, 0.34, 6) + _gc_dna(350, 0.72, 7), 1, 1)]
+    grad = "".join(_gc_dna(700, g, 10 + i) for i, g in enumerate((0.25, 0.32, 0.38, 0.44, 0.5, 0.56, 0.62, 0.56, 0.44, 0.32)))
+    ag5 = "".join(_ag_rich(1800, g, i, 4) for i, g in enumerate((0.34, 0.72, 0.34, 0.72, 0.34)))
+    ag4 = "".join(_ag_rich(2300, g, 10 + i, 4) for i, g in enumerate((0.70, 0.34, 0.70, 0.34)))
+    ag3 = "".join(_ag_rich(1200, g, 779858 + i, 3) for i, g in enumerate((0.34, 0.72, 0.34, 0.72, 0.34, 0.72)))
+    two = [(n, s, 0, 0) for n, s in replay_batch_pieces(2)]
+    return {
+        "human": two,
+        "human_w600": ends,
+        "nasonia_w1000": [("gradient", _gc_dna(1500, 0.25, 9) + grad + _gc_dna(1500, 0.3, 8), 0, 0)],
+        "human_utr": two[:2],
+        "human_utr_w600": ends + [("ag5", ag5, 0, 0), ("ag4", ag4, 0, 0), ("ag_end", ag4[:2300] + ag5[:1800] + "CAGAG", 0, 0), ("ag3", ag3, 0, 0)],
+    }
+
+
+_replay_models, _replay_twins = {}, {}
+
+
+def replay_model(cfg, **more):
+    import augustus_amd as ax
+    key = (cfg, tuple(sorted(more.items())))
+    if key not in _replay_models:
+        species, opts = REPLAY_CFGS[cfg]
+        _replay_models[key] = ax.Model(config_path(), species, **{**opts, **more})
+    return _replay_models[key]
+
+
+def replay_twin(cfg, case):
+    """(twin_decode's tuple with cells, {key: term}, site log, flushes) of one (name, sequence, init_kind, term_kind) under a
+    configuration of REPLAY_CFGS, with the twin's caches on; computed once per sequence"""
+    name, seq, ik, tk = case
+    key = (cfg, seq, ik, tk)
+    if key not in _replay_twins:
+        m = replay_model(cfg)
+        _replay_twins[key] = twin_cache_log(m.tables_ptr, seq, m.n_states, cells=True, init_kind=ik, term_kind=tk)
+    return _replay_twins[key]
+
+
+def assert_terms_equal(got, want, what):
+    """{key: term} against {key: term}: both directions, bit for bit"""
+    missing = sorted(set(want) - set(got))
+    extra = sorted(set(got) - set(want))
+    assert not missing and not extra, (what, "not patched", missing[:5], len(missing), "patched, not in the twin's log", extra[:5], len(extra))
+    wrong = [(k, got[k], want[k]) for k in want if got[k] != want[k]]
+    assert not wrong, (what, wrong[:5], len(wrong))
