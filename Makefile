@@ -9,9 +9,9 @@ ARCH    ?= gfx950
 HIPFLAGS = --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -Wno-unused-result
 CXXFLAGS = -O2 -std=c++17 -fPIC -ffp-contract=off
 SRC     = augustus_amd/csrc
-HOSTSRC = $(SRC)/model.cc $(SRC)/capi_model.cc $(SRC)/genes.cc $(SRC)/driver.cc $(SRC)/sharded.cc
+HOSTSRC = $(SRC)/model.cc $(SRC)/capi_model.cc $(SRC)/capi_genbank.cc $(SRC)/genes.cc $(SRC)/genbank.cc $(SRC)/evaluation.cc $(SRC)/driver.cc $(SRC)/sharded.cc
 DEVHDR  = $(SRC)/device/assmemo.h $(SRC)/device/dp.h $(SRC)/device/kernels.h $(SRC)/device/dense.h $(SRC)/device/layout.h $(SRC)/device/sampler.h $(SRC)/device/snipmemo.h $(SRC)/device/launch.h
-HOSTHDR = $(SRC)/model.h $(SRC)/genes.h $(SRC)/capi_internal.h include/augx.h
+HOSTHDR = $(SRC)/model.h $(SRC)/genes.h $(SRC)/genbank.h $(SRC)/evaluation.h $(SRC)/capi_internal.h include/augx.h
 
 all: product oracle emu
 product: augustus_amd/libaugx.so augustus_amd/libaugx_smallwin.so augustus_amd/bin/augustus

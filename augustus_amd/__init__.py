@@ -530,3 +530,176 @@ class Decoder:
             self.close()
         except Exception:
             pass
+
+
+# ---------------------------------------------------------------------------------------------------
+# GenBank input and accuracy evaluation (host only; include/augx.h: augx_genbank_*, augx_eval_*)
+# ---------------------------------------------------------------------------------------------------
+INPUT_UNKNOWN, INPUT_GENBANK, INPUT_FASTA = 0, 1, 2
+EXON_CDS, EXON_UTR5, EXON_UTR3 = 0, 1, 2
+
+
+class _Exon(ctypes.Structure):
+    _fields_ = [("begin", ctypes.c_int64), ("end", ctypes.c_int64), ("strand", ctypes.c_int32), ("frame", ctypes.c_int32), ("kind", ctypes.c_int32)]
+
+
+class _Transcript(ctypes.Structure):
+    _fields_ = [("gene_id", ctypes.c_char_p), ("transcript_id", ctypes.c_char_p), ("strand", ctypes.c_int32), ("complete", ctypes.c_int32),
+                ("complete_left", ctypes.c_int32), ("complete_right", ctypes.c_int32), ("complete_5utr", ctypes.c_int32), ("complete_3utr", ctypes.c_int32),
+                ("trans_start", ctypes.c_int64), ("trans_end", ctypes.c_int64), ("coding_start", ctypes.c_int64), ("coding_end", ctypes.c_int64),
+                ("n_exons", ctypes.c_int32), ("exons", ctypes.POINTER(_Exon))]
+
+
+class _PieceResult(ctypes.Structure):
+    _fields_ = [("record", ctypes.c_int32), ("status", ctypes.c_int32), ("begin", ctypes.c_int64), ("end", ctypes.c_int64),
+                ("states", ctypes.POINTER(_State)), ("n_states", ctypes.c_int32)]
+
+
+_TX_FIELDS = ("gene_id", "transcript_id", "strand", "complete", "complete_left", "complete_right", "complete_5utr", "complete_3utr",
+              "trans_start", "trans_end", "coding_start", "coding_end")
+
+
+def _gb_lib():
+    L = lib()
+    if not getattr(L, "_gb_bound", False):
+        L.augx_input_type.argtypes = [ctypes.c_char_p, ctypes.c_int64]
+        L.augx_genbank_read.argtypes = [ctypes.c_char_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]
+        L.augx_genbank_read_file.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]
+        L.augx_genbank_n_loci.argtypes = [ctypes.c_void_p]
+        L.augx_genbank_messages.restype = ctypes.c_char_p
+        L.augx_genbank_messages.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        L.augx_genbank_locus.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_char_p),
+                                         ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int)]
+        L.augx_genbank_transcript.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_Transcript)]
+        L.augx_genbank_format_annotation.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int64]
+        L.augx_genbank_destroy.argtypes = [ctypes.c_void_p]
+        L.augx_genbank_report.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_double, ctypes.c_char_p, ctypes.c_int64]
+        L.augx_eval_create.restype = ctypes.c_void_p
+        L.augx_eval_add.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]
+        L.augx_eval_print.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int64]
+        L.augx_eval_destroy.argtypes = [ctypes.c_void_p]
+        L._gb_bound = True
+    return L
+
+
+def input_type(data):
+    """FASTA, GenBank or neither (``augx_input_type``; reference ``GBSplitter::determineFileType``)."""
+    if isinstance(data, str):
+        data = data.encode()
+    return _gb_lib().augx_input_type(data, len(data))
+
+
+def _flat_transcripts(txs):
+    """ctypes array of augx_transcript from dicts with the fields of _TX_FIELDS and "exons": [(begin, end, kind)]; the second value keeps the
+    buffers alive"""
+    arr = (_Transcript * max(1, len(txs)))()
+    keep = []
+    for i, t in enumerate(txs):
+        ex = (_Exon * max(1, len(t["exons"])))()
+        for k, e in enumerate(t["exons"]):
+            ex[k].begin, ex[k].end, ex[k].kind = e[0], e[1], e[2]
+            ex[k].strand, ex[k].frame = t["strand"], -1
+        keep.append(ex)
+        for f in _TX_FIELDS:
+            v = t.get(f, None if f.endswith("_id") else -1 if f.endswith(("_start", "_end")) else 1)
+            setattr(arr[i], f, v.encode() if isinstance(v, str) else v)
+        arr[i].n_exons = len(t["exons"])
+        arr[i].exons = ctypes.cast(ex, ctypes.POINTER(_Exon))
+    return arr, keep
+
+
+class GenBank:
+    """The loci of a GenBank text with their annotated transcripts (``augx_genbank_read``; reference ``GBProcessor::getAnnoSequenceList``)."""
+
+    def __init__(self, data, utr=False, stop_excluded=False, verbosity=3):
+        L = _gb_lib()
+        if isinstance(data, str):
+            data = data.encode()
+        self._h = ctypes.c_void_p()
+        rc = L.augx_genbank_read(data, len(data), int(utr), int(stop_excluded), verbosity, ctypes.byref(self._h))
+        self.stdout = L.augx_genbank_messages(self._h, 1).decode() if self._h else ""
+        self.stderr = L.augx_genbank_messages(self._h, 2).decode() if self._h else ""
+        if rc != 0:
+            self.close()
+            raise AugxError(rc, L.augx_last_error().decode(errors="replace") + ("\n" + self.stderr if self.stderr else ""))
+
+    def __len__(self):
+        return _gb_lib().augx_genbank_n_loci(self._h)
+
+    def locus(self, i):
+        """(name, sequence, length, [transcript dict])"""
+        L = _gb_lib()
+        name, seq, n, nt = ctypes.c_char_p(), ctypes.c_char_p(), ctypes.c_int64(), ctypes.c_int()
+        _check(L.augx_genbank_locus(self._h, i, ctypes.byref(name), ctypes.byref(seq), ctypes.byref(n), ctypes.byref(nt)))
+        txs = []
+        for k in range(nt.value):
+            t = _Transcript()
+            _check(L.augx_genbank_transcript(self._h, i, k, ctypes.byref(t)))
+            d = {f: getattr(t, f) for f in _TX_FIELDS}
+            d["gene_id"], d["transcript_id"] = d["gene_id"].decode(), d["transcript_id"].decode()
+            d["exons"] = [(t.exons[q].begin, t.exons[q].end, t.exons[q].kind, t.exons[q].strand, t.exons[q].frame) for q in range(t.n_exons)]
+            txs.append(d)
+        return name.value.decode(), seq.value.decode(), n.value, txs
+
+    def annotation_gff(self, model, i):
+        """the annotation of locus i as the reference prints it (``AnnoSequence::printGFF``), with the model's output options"""
+        buf = ctypes.create_string_buffer(4 << 20)
+        _check(_gb_lib().augx_genbank_format_annotation(model._h, self._h, i, buf, len(buf)))
+        return buf.value.decode()
+
+    def report(self, model, pieces, seconds=0.0):
+        """the output of a run on this input from decoded pieces [(record, begin, end, status, [(begin, end, state, type)])]
+        (``augx_genbank_report``; reference ``evaluateOnTestSet``)"""
+        arr = (_PieceResult * max(1, len(pieces)))()
+        keep = []
+        for i, (rec, b, e, status, path) in enumerate(pieces):
+            sts = (_State * max(1, len(path)))()
+            for k, (pb, pe, s, ty) in enumerate(path):
+                sts[k].begin, sts[k].end, sts[k].state, sts[k].type = pb, pe, s, ty
+            keep.append(sts)
+            arr[i].record, arr[i].status, arr[i].begin, arr[i].end, arr[i].n_states = rec, status, b, e, len(path)
+            arr[i].states = ctypes.cast(sts, ctypes.POINTER(_State))
+        buf = ctypes.create_string_buffer(16 << 20)
+        _check(_gb_lib().augx_genbank_report(model._h, self._h, len(pieces), arr, seconds, buf, len(buf)))
+        return buf.value.decode()
+
+    def close(self):
+        if self._h:
+            _gb_lib().augx_genbank_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        if sys.is_finalizing():
+            return
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Evaluation:
+    """Accuracy of predicted against annotated transcripts (``augx_eval_*``; reference ``Evaluation``)."""
+
+    def __init__(self):
+        self._h = ctypes.c_void_p(_gb_lib().augx_eval_create())
+
+    def add(self, predicted, annotated, strand=0):
+        """one locus; transcripts as the dicts of :meth:`GenBank.locus`; strand 0 = both, +1 / -1 = that strand only"""
+        p, k1 = _flat_transcripts(predicted)
+        a, k2 = _flat_transcripts(annotated)
+        _check(_gb_lib().augx_eval_add(self._h, len(predicted), p, len(annotated), a, strand))
+
+    def report(self):
+        buf = ctypes.create_string_buffer(1 << 20)
+        _check(_gb_lib().augx_eval_print(self._h, buf, len(buf)))
+        return buf.value.decode()
+
+    def __del__(self):
+        if sys.is_finalizing():
+            return
+        try:
+            if self._h:
+                _gb_lib().augx_eval_destroy(self._h)
+                self._h = ctypes.c_void_p()
+        except Exception:
+            pass

@@ -1,7 +1,10 @@
 // capi_internal.h -- opaque handle definitions shared by the C-ABI translation units
 #pragma once
 #include <string>
+#include <vector>
 #include "model.h"
+#include "genbank.h"
+#include "evaluation.h"
 
 struct augx_model {
     augx::Model m;
@@ -10,6 +13,16 @@ struct augx_model {
 namespace augx {
 void setLastError(const std::string &m);
 }
+
+// a GenBank file that has been read (capi_genbank.cc): the loci, and the flat exon lists behind the pointers of augx_transcript
+struct augx_genbank {
+    augx::GbFile f;
+    std::vector<std::vector<std::vector<augx_exon>>> exons; // [locus][transcript]
+};
+struct augx_eval {
+    augx::Evaluation e;
+    bool printed = false;
+};
 
 // sampling in two halves (device/decoder.hip): what the sampler reads of a piece is fetched and indexed ahead of the sampling
 struct augx_sample_prep;

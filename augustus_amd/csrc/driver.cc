@@ -242,8 +242,17 @@ struct PieceOut {
 //      NAMGene::doViterbiPiecewise, src/namgene.cc:526,626-650; block headers src/augustus.cc:395-398).  `pieces` may
 //      arrive in any order (they were decoded on several devices): they are gathered by (record, begin) first.
 //      Returns 0, or 1 when the very first record failed (the reference then aborts the run, src/augustus.cc:425-440).
+//      A run on GenBank input (reference evaluateOnTestSet, src/augustus.cc:289-357) goes through the same steps with `gb`: the
+//      block header reads "sequence number", the annotation of the locus follows it, the predicted transcripts of every record
+//      are handed back (in the coordinates of the input: the reference shifts them by --predictionStart, src/namgene.cc:629)
+//      and any error ends the run (there is no try block around a locus).
+struct GenbankBlocks {
+    const std::vector<std::string> *annotation;        // per record: the text after "# annotation: "
+    std::vector<std::vector<Transcript>> *predicted;   // per record, out
+};
 int formatRecords(const Model &M, const OutputOptions &oo, const std::vector<RecordView> &recs, std::vector<PieceOut> pieces,
-                  int verbosity, int &geneid, std::string &out, std::string &err, std::string &fatal, int sampleiterations = 0) {
+                  int verbosity, int &geneid, std::string &out, std::string &err, std::string &fatal, int sampleiterations = 0,
+                  const GenbankBlocks *gb = nullptr) {
     std::stable_sort(pieces.begin(), pieces.end(), [](const PieceOut &a, const PieceOut &b) { return a.rec != b.rec ? a.rec < b.rec : a.begin < b.begin; });
     int successful = 0;
     const bool noInFrameStop = M.opt.getBool("noInFrameStop", false);
@@ -333,17 +342,28 @@ int formatRecords(const Model &M, const OutputOptions &oo, const std::vector<Rec
         }
         printGeneList(pieceText[i], genes, rec.seq, rec.len, oo, &pieceRuns);
     });
+    if (gb) {
+        gb->predicted->assign(recs.size(), {});
+        for (size_t i = 0; i < np; i++)
+            if (pieces[i].status == 0 && pieceErr[i].empty())
+                for (const GeneOut &g : pieceGenes[i])
+                    for (const Transcript &t : g.transcripts) {
+                        (*gb->predicted)[(size_t)pieces[i].rec].push_back(t);
+                        (*gb->predicted)[(size_t)pieces[i].rec].back().shift(oo.offset);
+                    }
+    }
     size_t pi = 0;
     for (size_t r = 0; r < recs.size(); r++) {
         const RecordView &rec = recs[r];
         if (verbosity) {
-            out += "#\n# ----- prediction on sequence number " + std::to_string(r + 1) + " (length = " + std::to_string(rec.len) + ", name = " + rec.name + ") -----\n#\n";
+            out += std::string("#\n# ----- ") + (gb ? "" : "prediction on ") + "sequence number " + std::to_string(r + 1) + " (length = " + std::to_string(rec.len) + ", name = " + rec.name + ") -----\n#\n";
+            if (gb) out += "\n# annotation: \n" + (*gb->annotation)[r];
         }
         {
             const std::string st = M.opt.get("strand", "both");
             const bool fw = st == "forward", bw = st == "backward"; // (other values fall back to both, see genes.cc)
             out += "# Predicted genes for sequence number " + std::to_string(r + 1) + " on " + (fw ? "forward strand" : bw ? "reverse strand" : "both strands") + "\n";
-            if (M.opt.getBool("singlestrand", false)) out += "# Overlapping genes on opposite strand are allowed.\n";
+            if (M.opt.getBool("singlestrand", false)) out += gb ? "# Overlapping genes on opposite strand were allowed.\n" : "# Overlapping genes on opposite strand are allowed.\n";
         }
         bool any = false;
         std::string errmsg;
@@ -362,7 +382,7 @@ int formatRecords(const Model &M, const OutputOptions &oo, const std::vector<Rec
             out += pieceText[pi];
         }
         if (!errmsg.empty()) {
-            if (successful < 1) { fatal = errmsg; return 1; }
+            if (successful < 1 || gb) { fatal = errmsg; return 1; }
             err += "\n augustus: ERROR\n\t" + errmsg + "\n\n";
         } else
             successful++;
@@ -709,6 +729,39 @@ bool findCutPoints(const Model &M, const std::vector<RecordView> &recs, long max
     return true;
 }
 
+// ---- the run on GenBank input after the decode (reference evaluateOnTestSet, src/augustus.cc:254-364): per locus the header, the
+//      annotation and the predicted genes; then the accuracy report and the time.  Options of that function this path does not
+//      build are refused by name.
+const char *genbankRefusal(const Model &M) {
+    if (M.opt.getBool("noprediction", false)) return "--noprediction=true (the annotation's own path and probability: training path) is outside the MI355X ab-initio hot path";
+    if (M.opt.getBool("checkExAcc", false)) return "--checkExAcc=true (accuracy of extrinsic evidence: hints path) is outside the MI355X ab-initio hot path";
+    return nullptr;
+}
+int genbankReport(const Model &M, const OutputOptions &oo, const std::vector<GbLocus> &loci, const std::vector<PieceOut> &po, int verbosity, int &geneid,
+                  int sampleiterations, double secondsBefore, std::string &text, std::string &errText, std::string &fatal) {
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<RecordView> rv;
+    std::vector<std::string> anno(loci.size());
+    for (size_t r = 0; r < loci.size(); r++) {
+        rv.push_back({loci[r].name.c_str(), loci[r].seq.data(), (long)loci[r].seq.size()});
+        printAnnotationGFF(anno[r], loci[r], oo); // (in the coordinates of the file, whatever --predictionStart says: the reference cuts the sequence only)
+    }
+    std::vector<std::vector<Transcript>> predicted;
+    const GenbankBlocks gb{&anno, &predicted};
+    if (formatRecords(M, oo, rv, po, verbosity, geneid, text, errText, fatal, sampleiterations, &gb)) return 1;
+    const std::string st = M.opt.get("strand", "both");
+    const int strand = st == "forward" ? 1 : st == "backward" ? -1 : 0;
+    const auto te = std::chrono::steady_clock::now();
+    Evaluation ev;
+    for (size_t r = 0; r < loci.size(); r++) ev.add(predicted[r], loci[r].genes, strand);
+    ev.finishAndPrint(text);
+    if (getenv("AUGX_TIMING")) fprintf(stderr, "augx timing:   evaluation of %zu loci: %.3f s\n", loci.size(), std::chrono::duration<double>(std::chrono::steady_clock::now() - te).count());
+    char buf[64];
+    snprintf(buf, sizeof buf, "%.3g", secondsBefore + std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+    text += std::string("# total time: ") + buf + "\n";
+    return 0;
+}
+
 } // namespace
 
 extern "C" int augx_main(int argc, const char *const *argv) {
@@ -824,6 +877,28 @@ extern "C" int augx_main(int argc, const char *const *argv) {
             }
         }
     }
+    // The type of the input is found before the model is loaded: for GenBank input soft-masking is off unless it was asked for
+    // (reference src/augustus.cc:218-219, Constant::softmasking_explicitly_requested), and the model reads that option.  A file
+    // that begins with '>' is FASTA and is read later as before; standard input is FASTA (reference src/genbank.cc:547-551).
+    bool genbank = false, softDefaultOn = true;
+    std::string gbText;
+    if (!queryfile.empty() && queryfile != "-") {
+        std::ifstream in(queryfile.c_str());
+        if (in && (in >> std::ws) && in.peek() != '>' && in.peek() != EOF) {
+            in.seekg(0);
+            std::ostringstream ss;
+            ss << in.rdbuf();
+            gbText = ss.str();
+            genbank = augx_input_type(gbText.data(), (int64_t)gbText.size()) == AUGX_INPUT_GENBANK;
+            if (!genbank) gbText.clear();
+        }
+    }
+    if (genbank) {
+        bool given = false;
+        for (auto &kv : cmd)
+            if (kv.first == "softmasking") { given = true; softDefaultOn = false; }
+        if (!given) cmd.push_back({"softmasking", "0"});
+    }
     std::vector<const char *> names, values;
     for (auto &kv : cmd) { names.push_back(kv.first.c_str()); values.push_back(kv.second.c_str()); }
     int rc = augx_model_load(configPath.c_str(), species.c_str(), (int)cmd.size(), names.data(), values.data(), &S.model);
@@ -832,6 +907,8 @@ extern "C" int augx_main(int argc, const char *const *argv) {
     const Model &M = S.model->m;
     S.oo.fromModel(M);
     if (queryfile.empty()) return fail("No query file specified. Type \"augustus\" for help.");
+    if (genbank)
+        if (const char *why = genbankRefusal(M)) return fail(why);
     if (queryfile != "-") { // (reference: the input file is opened before the header is printed)
         std::ifstream probe(queryfile.c_str());
         if (!probe) return fail("Could not open input file \"" + queryfile + "\"!");
@@ -868,6 +945,9 @@ extern "C" int augx_main(int argc, const char *const *argv) {
               << "# Using native and syntenically mapped cDNA alignments to improve de novo gene finding\n"
               << "# Bioinformatics 24: 637-644, doi 10.1093/bioinformatics/btn013" << std::endl;
     if (verbosity) std::cout << "# No extrinsic information on sequences given." << std::endl;
+    // (GenBank input: the reference has read its extrinsic configuration for the soft-masking hints by now and says so, although the
+    //  hints are then left out, src/augustus.cc:218-219)
+    if (genbank && verbosity && (softDefaultOn || S.oo.softmasking)) std::cout << "# Sources of extrinsic information: M RM " << std::endl;
     if (verbosity > 1) std::cout << "# Initializing the parameters using config directory " << configPath << " ..." << std::endl;
     std::cout << "# " << species << " version.";
     if (M.speciesSpecificTrans) std::cout << " Using species specific transition matrix: " << M.transFileUsed;
@@ -877,7 +957,36 @@ extern "C" int augx_main(int argc, const char *const *argv) {
     if (M.temperature && verbosity) std::cout << "# setting temperature to " << M.temperature << " (for sampling)" << std::endl;
 
     std::vector<Record> recs;
-    {
+    std::vector<GbLocus> loci; // GenBank input: the annotated loci, recs[i] = (name, sequence) of loci[i]
+    if (genbank) {
+        if (verbosity > 2) std::cout << "# Looks like " << queryfile << " is in genbank format. Augustus uses the annotation for evaluation of accuracy." << std::endl;
+        augx_genbank *g = nullptr;
+        const std::string utrOpt = M.opt.get("UTR", "");
+        rc = augx_genbank_read(gbText.data(), (int64_t)gbText.size(), utrOpt == "both" || utrOpt == "1" || utrOpt == "on" || utrOpt == "5",
+                               M.opt.getBool("stopCodonExcludedFromCDS", false), M.opt.getInt("/genbank/verbosity", 3), &g);
+        if (g) {
+            std::cout << augx_genbank_messages(g, 1) << std::flush;
+            std::cerr << augx_genbank_messages(g, 2) << std::flush;
+        }
+        if (rc) { const std::string why = augx_last_error(); augx_genbank_destroy(g); restore(); return fail(why); }
+        loci = std::move(g->f.loci);
+        augx_genbank_destroy(g);
+        gbText.clear();
+        if (S.oo.softmasking) { // reference warnAllLowerCase, src/gene.cc:2968-2993
+            bool allLower = true;
+            for (size_t r = 0; r < loci.size() && allLower; r++)
+                for (char c : loci[r].seq)
+                    if (isupper((unsigned char)c)) { allLower = false; break; }
+            if (allLower)
+                std::cerr << "#########################################################################" << std::endl
+                          << "# WARNING: --softmasking=1 and all sequences are completely in lower case." << std::endl
+                          << "# They will be treated as repeatmasked everywhere and genes could be severely underpredicted." << std::endl
+                          << "# If this is not intended, rerun with --softmasking=0" << std::endl
+                          << "#########################################################################" << std::endl;
+        }
+        for (GbLocus &l : loci) recs.push_back({l.name, l.seq});
+        lap("GenBank read");
+    } else {
         bool ok;
         if (queryfile == "-") ok = readFasta(std::cin, recs);
         else {
@@ -887,12 +996,14 @@ extern "C" int augx_main(int argc, const char *const *argv) {
         }
         if (!ok) { restore(); return fail("File format of " + queryfile + " not recognized (only FASTA input is supported on the MI355X path)."); }
     }
-    lap("FASTA read");
-    if (verbosity > 2) {
-        if (queryfile == "-") std::cout << "# Reading sequences from standard input. Assuming fasta format." << std::endl;
-        else std::cout << "# Looks like " << queryfile << " is in fasta format." << std::endl;
+    if (!genbank) {
+        lap("FASTA read");
+        if (verbosity > 2) {
+            if (queryfile == "-") std::cout << "# Reading sequences from standard input. Assuming fasta format." << std::endl;
+            else std::cout << "# Looks like " << queryfile << " is in fasta format." << std::endl;
+        }
+        if (verbosity > 0) std::cout << "# We have hints for 0 sequences and for 0 of the sequences in the input set." << std::endl;
     }
-    if (verbosity > 0) std::cout << "# We have hints for 0 sequences and for 0 of the sequences in the input set." << std::endl;
 
     const long maxstep = M.opt.getInt("maxDNAPieceSize", 1000000);
     if (maxstep < 1000) { std::cerr << "maxDNAPieceSize is too small: " << maxstep << std::endl; restore(); S.destroy(); return 1; }
@@ -953,10 +1064,16 @@ extern "C" int augx_main(int argc, const char *const *argv) {
             }
             recs[0].seq = recs[0].seq.substr((size_t)ps, (size_t)(pe - ps + 1));
             S.oo.offset = ps;
+            if (genbank) { // (the annotation keeps the coordinates of the file; the locus has the length of the piece from here on)
+                loci.resize(1);
+                loci[0].seq = recs[0].seq;
+                loci[0].length = (long)recs[0].seq.size();
+            }
         } else if (ps < 0 && pe < 0 && pe == ps)
             S.oo.offset = -ps - 1;
     }
     const bool soft = S.oo.softmasking;
+    const double tPredict0 = now(); // ("# total time" of a run on GenBank input: the prediction, from here to the last gene)
 
     // ---- phase 1: find the cut points of all records (findCutPoints above; every exam window is decoded on the GPUs)
     std::vector<std::vector<PieceRef>> recPieces;
@@ -1108,7 +1225,8 @@ extern "C" int augx_main(int argc, const char *const *argv) {
         po.swap(merged);
     }
     std::string text, errText, fatal;
-    if (formatRecords(M, S.oo, rv, po, verbosity, S.geneid, text, errText, fatal, S.sampleiterations)) {
+    if (genbank ? genbankReport(M, S.oo, loci, po, verbosity, S.geneid, S.sampleiterations, now() - tPredict0, text, errText, fatal)
+                : formatRecords(M, S.oo, rv, po, verbosity, S.geneid, text, errText, fatal, S.sampleiterations)) {
         std::cout << text;
         std::cerr << errText;
         restore();
@@ -1213,6 +1331,37 @@ extern "C" int augx_format_records(const augx_model *m, int n_records, const cha
         int rc = formatRecords(m->m, oo, rv, po, 1, geneid, text, errText, fatal);
         if (rc) { setLastError(fatal); return AUGX_E_NOPATH; }
         if ((int64_t)text.size() + 1 > out_cap) { setLastError("augx_format_records: output buffer too small"); return AUGX_E_ARG; }
+        memcpy(out, text.c_str(), text.size() + 1);
+        return AUGX_OK;
+    } catch (std::exception &e) {
+        setLastError(e.what());
+        return AUGX_E_CONFIG;
+    }
+}
+
+// ---- the output of a run on GenBank input from pieces decoded anywhere: what augx_main prints between "# Read in n genbank
+//      sequences." and "# command line:" (the Viterbi paths alone: a model with --sample > 0 needs the sampled paths, which
+//      augx_main has and this entry does not take)
+extern "C" int augx_genbank_report(const augx_model *m, const augx_genbank *g, int n_pieces, const augx_piece_result *pieces, double seconds,
+                                   char *out, int64_t out_cap) {
+    if (!m || !g || n_pieces < 0 || !out || (n_pieces && !pieces)) { setLastError("augx_genbank_report: bad argument"); return AUGX_E_ARG; }
+    try {
+        const Model &M = m->m;
+        if (const char *why = genbankRefusal(M)) { setLastError(why); return AUGX_E_UNSUPPORTED; }
+        if (M.opt.getInt("sample", 0) >= 10) { setLastError("augx_genbank_report: the model samples (--sample); only Viterbi paths can be handed in"); return AUGX_E_ARG; }
+        OutputOptions oo;
+        oo.fromModel(M);
+        std::vector<std::vector<PathState>> paths(n_pieces);
+        std::vector<PieceOut> po;
+        for (int i = 0; i < n_pieces; i++) {
+            if (pieces[i].record < 0 || pieces[i].record >= (int)g->f.loci.size()) { setLastError("augx_genbank_report: bad record index"); return AUGX_E_ARG; }
+            for (int k = 0; k < pieces[i].n_states; k++) paths[i].push_back({pieces[i].states[k].begin, pieces[i].states[k].end, pieces[i].states[k].type});
+            po.push_back({pieces[i].record, (long)pieces[i].begin, (long)pieces[i].end, &paths[i], pieces[i].status});
+        }
+        int geneid = 1;
+        std::string text, errText, fatal;
+        if (genbankReport(M, oo, g->f.loci, po, M.opt.getInt("/augustus/verbosity", 1), geneid, 0, seconds, text, errText, fatal)) { setLastError(fatal); return AUGX_E_NOPATH; }
+        if ((int64_t)text.size() + 1 > out_cap) { setLastError("augx_genbank_report: output buffer too small"); return AUGX_E_ARG; }
         memcpy(out, text.c_str(), text.size() + 1);
         return AUGX_OK;
     } catch (std::exception &e) {

@@ -648,9 +648,8 @@ static void appendf(std::string &out, const char *fmt, ...) {
 }
 
 // reference Gene::printGFF, src/gene.cc:1998-2313 (coding genes without UTR)
-static void printTranscriptGFF(std::string &out, const Transcript &t, const OutputOptions &o) {
+void printTranscriptGFF(std::string &out, const Transcript &t, const OutputOptions &o, const char *source) {
     const char *seqname = t.seqname.c_str();
-    const char *source = "AUGUSTUS";
     const char strand = t.plus ? '+' : '-';
     std::string transcript_id = t.geneid + "." + t.id;
     std::string parentstr = o.gff3 ? ("Parent=" + transcript_id) : ("transcript_id \"" + transcript_id + "\"; gene_id \"" + t.geneid + "\";");

@@ -99,6 +99,10 @@ void reverseGenes(std::vector<GeneOut> &genes, long endpos);
 void printGeneList(std::string &out, const std::vector<GeneOut> &genes, const char *seq, long seqlen, const OutputOptions &o,
                    const std::vector<std::pair<long, long>> *rmRuns = nullptr);
 
+// the feature lines of one transcript (reference Gene::printGFF, src/gene.cc:1998-2250); source: column 2 -- "AUGUSTUS" for a
+// prediction, "database" for an annotated gene of a GenBank locus (genbank.cc)
+void printTranscriptGFF(std::string &out, const Transcript &t, const OutputOptions &o, const char *source = "AUGUSTUS");
+
 std::string translateCDS(const char *codingSeq, const char *table = nullptr); // (table: 64 letters by codon index, null: the standard code)
 
 } // namespace augx

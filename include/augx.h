@@ -400,6 +400,62 @@ typedef struct augx_piece_result {
 int augx_format_records(const augx_model *m, int n_records, const char *const *names, const char *const *seqs,
                         const int64_t *lens, int n_pieces, const augx_piece_result *pieces, char *out, int64_t out_cap);
 
+/* ---- GenBank query files (replaces GBProcessor: fileType / getAnnoSequenceList, reference include/genbank.hh:137-170,
+ *      src/genbank.cc:40-367, 542-759).  Host only: no device is needed.  augx_main reads its GenBank input through these. ---- */
+enum { AUGX_INPUT_UNKNOWN = 0, AUGX_INPUT_GENBANK = 1, AUGX_INPUT_FASTA = 2 };   /* reference FileType, include/genbank.hh:27 */
+/* reference GBSplitter::determineFileType, src/genbank.cc:585-634 */
+int augx_input_type(const char *data, int64_t len);
+enum { AUGX_EXON_CDS = 0, AUGX_EXON_UTR5 = 1, AUGX_EXON_UTR3 = 2 };
+typedef struct augx_exon {           /* reference State as an exon of a Gene, include/gene.hh:107-190 */
+    int64_t begin, end;              /* 0-based, inclusive, on the forward strand of the locus                         */
+    int32_t strand;                  /* +1 / -1                                                                        */
+    int32_t frame;                   /* CDS: the GFF frame column (bases before the first complete codon); else -1      */
+    int32_t kind;                    /* AUGX_EXON_*                                                                    */
+} augx_exon;
+typedef struct augx_transcript {     /* reference Gene, include/gene.hh:351-445                                        */
+    const char *gene_id, *transcript_id;   /* may be NULL in transcripts handed in                                     */
+    int32_t strand;                  /* +1 / -1                                                                        */
+    int32_t complete;                /* Transcript::complete: the coding region is complete (read of predictions)      */
+    int32_t complete_left, complete_right; /* the feature had no '<' / '>' (GBFeature::complete_l / complete_r)          */
+    int32_t complete_5utr, complete_3utr;  /* Gene::complete5utr / complete3utr                                          */
+    int64_t trans_start, trans_end;  /* Transcript::transstart / transend, -1: not known                               */
+    int64_t coding_start, coding_end;/* Gene::codingstart / codingend, -1: no coding exon                              */
+    int32_t n_exons;
+    const augx_exon *exons;          /* the 5'UTR exons, the CDS exons and the 3'UTR exons, each kind from left to right */
+} augx_transcript;
+typedef struct augx_genbank augx_genbank;
+/* reads every locus of a GenBank text (reference GBProcessor::getAnnoSequenceList).  utr: mRNA features become UTR exons (--UTR on);
+ * stop_excluded: --stopCodonExcludedFromCDS; verbosity: /genbank/verbosity (3).  AUGX_E_CONFIG with the reference's message when no
+ * locus could be read.  A locus the reference drops is dropped, with the reference's lines in the messages. */
+int augx_genbank_read(const char *data, int64_t len, int utr, int stop_excluded, int verbosity, augx_genbank **out);
+int augx_genbank_read_file(const char *path, int utr, int stop_excluded, int verbosity, augx_genbank **out);
+int augx_genbank_n_loci(const augx_genbank *g);
+/* what the reference's reader wrote while it read: stream 1 its output, 2 its error stream */
+const char *augx_genbank_messages(const augx_genbank *g, int stream);
+/* one locus (reference AnnoSequence, include/gene.hh:624-660): name, sequence (case kept; *len bases) and the number of annotated transcripts */
+int augx_genbank_locus(const augx_genbank *g, int locus, const char **name, const char **seq, int64_t *len, int *n_transcripts);
+/* annotated transcript k of a locus; the pointers inside live as long as g */
+int augx_genbank_transcript(const augx_genbank *g, int locus, int k, augx_transcript *out);
+/* the annotation of a locus as GFF (replaces AnnoSequence::printGFF, reference src/gene.cc:2918-2930), with the model's output options */
+int augx_genbank_format_annotation(const augx_model *m, const augx_genbank *g, int locus, char *out, int64_t out_cap);
+void augx_genbank_destroy(augx_genbank *g);
+
+/* ---- accuracy of a prediction against the annotation (replaces Evaluation: addToEvaluation, finishEvaluation, printQuotients,
+ *      print -- reference include/evaluation.hh:28-143, src/evaluation.cc:18-841; the accuracy of extrinsic evidence is not built) ---- */
+typedef struct augx_eval augx_eval;
+augx_eval *augx_eval_create(void);
+/* one locus: strand 0 = both, +1 / -1 = the genes of that strand only (--strand) */
+int augx_eval_add(augx_eval *e, int n_pred, const augx_transcript *pred, int n_anno, const augx_transcript *anno, int strand);
+/* finishes the evaluation and writes the reference's report (TSS / TTS distances, path quotients, the tables); once per object */
+int augx_eval_print(augx_eval *e, char *out, int64_t out_cap);
+void augx_eval_destroy(augx_eval *e);
+
+/* ---- the output of a run on GenBank input from pieces decoded anywhere (replaces evaluateOnTestSet, reference src/augustus.cc:254-364):
+ *      per locus the header, the annotation and the predicted genes, then the report and "# total time: <seconds>".  augx_main
+ *      prints exactly this text after its decode; with the pieces of the emulator it runs without a device. ---- */
+int augx_genbank_report(const augx_model *m, const augx_genbank *g, int n_pieces, const augx_piece_result *pieces, double seconds,
+                        char *out, int64_t out_cap);
+
 const char *augx_last_error(void);
 const char *augx_version(void);
 
