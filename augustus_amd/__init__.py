@@ -79,6 +79,8 @@ def lib():
         L.augx_batch_cells.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
         L.augx_batch_prep.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
                                       ctypes.POINTER(ctypes.c_int64)]
+        L.augx_batch_near_ties.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        L.augx_decoder_set_near_tie_eps.argtypes = [ctypes.c_void_p, ctypes.c_double]
         L.augx_batch_replay_counters.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_longlong)]
         L.augx_batch_replay_patches.restype = L.augx_batch_replay_sites.restype = ctypes.c_int64
         L.augx_batch_replay_patches.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]
@@ -161,6 +163,9 @@ PREP_ARRAYS = {
     "gcPlane": (4, "u1", 1, "bases"), "fx": (5, "u8", 20, "slots"), "sig": (6, "f8", 10, "bases"), "gate": (7, "u8", 1, "bases"),
     "plsR": (8, "f8", 3, "bases"), "ufx": (9, "u8", 6, "slots"), "ucnt": (10, "u4", 4, "slots"), "cls": (11, "i4", 1, "piece"),
     "nPlanes": (12, "i4", 1, "piece"), "planeCls": (13, "i4", 16, "piece"), "listCnt": (14, "i4", 1, "piece"),
+    # the back pointers of the chain states as the last decode left them (near-tie flag: bit 7 / bit 6); bpD has one byte per state of
+    # the model: handed out flat, [bases * S]
+    "bpChain": (15, "u1", 8, "bases"), "bpD": (16, "u1", 1, "bases"),
 }
 
 
@@ -249,6 +254,13 @@ class Batch:
         decode left it, plane ``plane`` of the arrays that have one per GC class of the piece (fx, plsR)"""
         L = lib()
         return prep_fetch(lambda w, pl, out, cap, nb: L.augx_batch_prep(self.decoder._h, self._h, piece, w, pl, out, cap, nb), which, plane)
+
+    def near_ties(self):
+        """test hook (``augx_batch_near_ties``): the near ties the back-trace of the last decode counted on the path of every piece"""
+        import numpy as np
+        out = np.zeros(self.n, dtype=np.int32)
+        _check(lib().augx_batch_near_ties(self.decoder._h, self._h, out.ctypes.data_as(ctypes.c_void_p)))
+        return [int(x) for x in out]
 
     def replay_hooks(self):
         """test hooks (``augx_batch_replay_counters`` / ``_patches`` / ``_sites``; decoder created with AUGX_DEBUG_CELLS=1): three callables
@@ -492,6 +504,10 @@ class Decoder:
     def count_near_ties(self, on=True):
         """``augx_decoder_count_near_ties``: batches created from now on count the near ties on their chosen paths"""
         _check(lib().augx_decoder_count_near_ties(self._h, 1 if on else 0))
+
+    def set_near_tie_eps(self, eps):
+        """``augx_decoder_set_near_tie_eps``: batches created from now on flag and count near ties by this threshold (2e-7 by default)"""
+        _check(lib().augx_decoder_set_near_tie_eps(self._h, float(eps)))
 
     def near_ties(self):
         """``augx_decoder_near_ties``: (cells, pieces) summed over the paths fetched so far"""

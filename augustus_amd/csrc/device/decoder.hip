@@ -482,6 +482,7 @@ struct augx_decoder {
     bool dense = false;        // the model is decoded by the dense kernels (dense.h)
     bool countNearTies = false;    // the back-trace counts the near ties on the chosen paths (AUGX_NEAR_TIES=1, augx_decoder_count_near_ties)
     int64_t nearTies = 0, nearTiePieces = 0; // ... summed over the batches whose paths were fetched
+    double nearTieEps = augx::dev::AUGX_NEAR_TIE; // the threshold the batches created from now on count by (augx_decoder_set_near_tie_eps)
     double mallocSeconds = 0, mallocBytes = 0; // hipMalloc calls of this decoder so far (AUGX_TIMING; under poolMu: the replay helpers allocate from many threads)
     bool exactMulti = true;    // replay the reference's snippet cache on multi-class pieces for the Viterbi run as well (augx_decoder_set_exact)
 };
@@ -768,6 +769,11 @@ int augx_decoder_set_share(augx_decoder *d, int n) {
 }
 
 int augx_decoder_count_near_ties(augx_decoder *d, int on) { if (!d) return AUGX_E_ARG; d->countNearTies = on != 0; return AUGX_OK; }
+int augx_decoder_set_near_tie_eps(augx_decoder *d, double eps) {
+    if (!d || !std::isfinite(eps) || !(eps > 0.0)) { setLastError("augx_decoder_set_near_tie_eps: the threshold must be finite and positive"); return AUGX_E_ARG; }
+    d->nearTieEps = eps;
+    return AUGX_OK;
+}
 int64_t augx_decoder_near_ties(const augx_decoder *d, int64_t *pieces) { if (pieces) *pieces = d ? d->nearTiePieces : 0; return d ? d->nearTies : 0; }
 int augx_decoder_exact(const augx_decoder *d) { return d && d->exactMulti ? 1 : 0; }
 int augx_decoder_set_exact(augx_decoder *d, int on) {
@@ -921,6 +927,7 @@ int augx_batch_create(augx_decoder *d, const augx_piece *pieces, int n, augx_bat
     }
     if (d->debugCells || d->dense) keep(V.cells, Z.N * d->hostT.S);
     if (d->countNearTies) keep(V.nearTie, n);
+    V.nearTieEps = d->nearTieEps;
     if (getenv("AUGX_PROF")) { keep(V.prof, (int64_t)n * 56 + 64); if (!rc && hipMemset(V.prof, 0, ((size_t)n * 56 + 64) * 8) != hipSuccess) { setLastError("augx_batch_create: hipMemset failed"); return AUGX_E_HIP; } }
     if (!d->dense) { keep(V.vig, Z.N); keep(V.longV, Z.N * 6); }
     keep(V.listCnt, n); keep(b->dListOffs, n + 1);
@@ -1501,11 +1508,22 @@ int augx_batch_prep(augx_decoder *d, augx_batch *b, int piece, int which, int pl
     case AUGX_PREP_NPLANES: perPiece(V.nPlanes, 1); break;
     case AUGX_PREP_PLANECLS: perPiece(V.planeCls, MAXPL); break;
     case AUGX_PREP_LISTCNT: perPiece(V.listCnt, 1); break;
+    case AUGX_PREP_BPCHAIN: if (V.bpChain) basesOf(V.bpChain, 1, 8, len); break;
+    case AUGX_PREP_BPD: if (V.bpD) basesOf(V.bpD, 1, d->hostT.S, len); break;
     }
     if (!src) { setLastError("augx_batch_prep: the model has no such array"); return AUGX_E_ARG; }
     *n_bytes = bytes;
     if (!out || cap_bytes < bytes) { setLastError("augx_batch_prep: the buffer is too small"); return AUGX_E_ARG; }
     HIP_TRY(hipMemcpy(out, src, (size_t)bytes, hipMemcpyDeviceToHost));
+    return AUGX_OK;
+}
+
+int augx_batch_near_ties(augx_decoder *d, augx_batch *b, int32_t *out) {
+    if (!d || !b || !out || !b->decoded) { setLastError("augx_batch_near_ties: bad argument, or the batch has not been decoded"); return AUGX_E_ARG; }
+    if (!b->V.nearTie) { setLastError("augx_batch_near_ties: the batch was created while the decoder did not count near ties"); return AUGX_E_ARG; }
+    HIP_TRY(hipSetDevice(d->device));
+    HIP_TRY(hipStreamSynchronize(d->stream));
+    HIP_TRY(hipMemcpy(out, b->V.nearTie, sizeof(int32_t) * (size_t)b->V.nPieces, hipMemcpyDeviceToHost));
     return AUGX_OK;
 }
 

@@ -1057,7 +1057,7 @@ AUGX_KFN void densePiece(const DevTables &T, const BatchView &B, DenseLds &L, in
             }
             (*lp(&L.ring[j & 63][s2])) = f;
             // (near ties are being counted, dp.h: AUGX_NEAR_TIE: bit 6 of the back pointer says that the runner-up was that close)
-            if (TIES && !FWD && fa < 8 && f2 > AUGX_NINF && f - f2 < AUGX_NEAR_TIE) fa |= 0x40;
+            if (TIES && !FWD && fa < 8 && f2 > AUGX_NINF && f - f2 < B.nearTieEps) fa |= 0x40;
             if (f > AUGX_NINF) { gp(M)[(int64_t)j * S + s2] = f; if (!FWD && BP) gp(BP)[(int64_t)j * S + s2] = (uint8_t)fa; }
         }
     };
@@ -1083,7 +1083,7 @@ AUGX_KFN void densePiece(const DevTables &T, const BatchView &B, DenseLds &L, in
                 else if (x > f || (x == f && selfAi < fa)) { if (TIES) f2 = f; f = x; fa = selfAi; }
                 else if (TIES) f2 = x;
             }
-            if (TIES && !FWD && fa < 8 && f2 > AUGX_NINF && f - f2 < AUGX_NEAR_TIE) fa |= 0x40;
+            if (TIES && !FWD && fa < 8 && f2 > AUGX_NINF && f - f2 < B.nearTieEps) fa |= 0x40;
             (*lp(&L.ring[j & 63][s2])) = f;
             if (f > AUGX_NINF) { gp(M)[(int64_t)j * S + s2] = f; if (!FWD && BP) gp(BP)[(int64_t)j * S + s2] = (uint8_t)fa; }
             prev = f;
@@ -1476,7 +1476,7 @@ AUGX_KFN void denseBacktracePiece(const DevTables &T, const BatchView &B, int p)
                 if (pass == 0) { if (better(b2.v, b2.key, best.v, best.key)) best = b2; }
                 else if (b2.v > runnerUp) runnerUp = b2.v;
             }
-            if (B.nearTie && runnerUp > AUGX_NINF && best.v - runnerUp < AUGX_NEAR_TIE && best.v != runnerUp) nearTies++; // (an exact tie is decided by the reference's own rule, the same in both)
+            if (B.nearTie && runnerUp > AUGX_NINF && best.v - runnerUp < B.nearTieEps && best.v != runnerUp) nearTies++; // (an exact tie is decided by the reference's own rule, the same in both)
             if (!(best.v > AUGX_NINF)) { overflow = true; break; }
             ai = best.aux; eop = best.key - KEY_BIAS;
         } else {
@@ -1515,7 +1515,7 @@ AUGX_KFN void denseBacktracePiece(const DevTables &T, const BatchView &B, int p)
                 if (pass == 0) { if (better(b2.v, b2.key, best.v, best.key)) best = b2; }
                 else if (b2.v > runnerUp) runnerUp = b2.v;
             }
-            if (B.nearTie && runnerUp > AUGX_NINF && best.v - runnerUp < AUGX_NEAR_TIE && best.v != runnerUp) nearTies++; // (an exact tie is decided by the reference's own rule, the same in both)
+            if (B.nearTie && runnerUp > AUGX_NINF && best.v - runnerUp < B.nearTieEps && best.v != runnerUp) nearTies++; // (an exact tie is decided by the reference's own rule, the same in both)
             if (!(best.v > AUGX_NINF)) { overflow = true; break; }
             ai = best.aux; eop = best.key / AUGX_MAX_ANC - KEY_BIAS;
         }

@@ -269,6 +269,8 @@ struct BatchView {
     int32_t *finalState;       // [nPieces]
     int32_t *pathRec;          // [N/8 + 64*nPieces][3]  (begin, end, state), reverse order per piece
     int32_t *pathCount;        // [nPieces]
+    double nearTieEps;         // the near-tie threshold of this batch (AUGX_NEAR_TIE unless augx_decoder_set_near_tie_eps chose another); read only
+                               // where near ties are counted: the TIES builds of the trellis / dense kernels and the back-trace under nearTie != NULL
 };
 
 AUGX_HD int mod3(int k) { return k >= 0 ? k % 3 : (k % 3 + 3) % 3; }

@@ -2305,7 +2305,7 @@ AUGX_KFN void trellisPiece(const DevTables &T, const BatchView &B, TrellisLds &L
                                          // ancestor, staying, best way in from a later ancestor) that close?  Bit 7 of the compact back pointer says so
                 const double o1 = gw == 0 ? vs : TX(bB), o2 = gw == 2 ? vs : TX(bA);
                 const double m2 = o1 > o2 ? o1 : o2;
-                if (m2 > AUGX_NINF && best - m2 < AUGX_NEAR_TIE) TX(rai) = bai | 0x80;
+                if (m2 > AUGX_NINF && best - m2 < B.nearTieEps) TX(rai) = bai | 0x80;
             }
         }
         FOR_WLANES(t, w) {
@@ -3529,7 +3529,7 @@ AUGX_KFN void backtracePiece(const DevTables &T, const BatchView &B, int p) {
                 if (pass == 0) { if (better(b2.v, b2.key, best.v, best.key)) best = b2; }
                 else if (b2.v > runnerUp) runnerUp = b2.v;
             }
-            if (B.nearTie && runnerUp > AUGX_NINF && best.v - runnerUp < AUGX_NEAR_TIE && best.v != runnerUp) nearTies++; // (an exact tie is decided by the reference's own rule, the same in both)
+            if (B.nearTie && runnerUp > AUGX_NINF && best.v - runnerUp < B.nearTieEps && best.v != runnerUp) nearTies++; // (an exact tie is decided by the reference's own rule, the same in both)
             if (!(best.v > AUGX_NINF)) { overflow = true; break; }
             ai = best.aux;
             eop = best.key - KEY_BIAS;

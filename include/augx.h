@@ -249,6 +249,11 @@ int augx_decoder_exact(const augx_decoder *d); /* the current setting (1 / 0) */
  * runs a build of the kernels of its own (about 1.5 % slower); off by default. */
 int augx_decoder_count_near_ties(augx_decoder *d, int on);
 int64_t augx_decoder_near_ties(const augx_decoder *d, int64_t *pieces /* may be NULL */);
+/* The threshold of the counter, 2e-7 unless set here: the batches created from now on flag and count by eps (as
+ * augx_decoder_count_near_ties applies to the batches created afterwards).  Only the kernels that count read it; the product's default
+ * kernels are the same with any value.  A test aid (tests/test_gpu_ties.py runs the counter at thresholds where real inputs have near
+ * ties); AUGX_E_ARG unless eps is finite and positive */
+int augx_decoder_set_near_tie_eps(augx_decoder *d, double eps);
 /* host buffers kept between sampled pieces (forward matrices, at most 12 GB) are released when the last decoder is destroyed, or here */
 void augx_release_host_pools(void);
 int64_t augx_decoder_batch_capacity(augx_decoder *d);
@@ -328,12 +333,24 @@ int augx_batch_cells(augx_decoder *d, augx_batch *b, int piece, double *out);
  *     in the device layout (chunks of 1024 slots, field-major inside a chunk);
  *   GCPLANE, SIG (10 doubles per base), GATE, PLSR of one plane (3 doubles per base): the len bases of the piece;
  *   GCRAW: the class of every GC window of the piece, len - win + 1 window starts (win = GCwinsize, at most len);
- *   CLS, NPLANES, PLANECLS (AUGX_MAX_CLASSES entries), LISTCNT: the per-piece scalars, int32.
+ *   CLS, NPLANES, PLANECLS (AUGX_MAX_CLASSES entries), LISTCNT: the per-piece scalars, int32;
+ *   and two arrays of the LAST DECODE of the batch, the len bases of the piece, which live as long as the batch and are rewritten by its next
+ *   decode only (the forward pass, the sampler and augx_batch_paths do not touch them):
+ *   BPCHAIN (trellis kernels only; 8 bytes per base): the back pointer of every single-base chain state, byte c = the c-th reachable chain
+ *     state in the order of the state index: 0xFF no value, else bits 0-6 the index of the winning ancestor, bit 7 the near-tie flag
+ *     (set only by a decoder that counts near ties);
+ *   BPD (dense kernels only; S bytes per base): the back pointers of the chain and fixed-lag states: 0xFF none, 0xFE a piece of N only, else
+ *     bits 0-5 the index of the winning ancestor, bit 6 the near-tie flag (chain states only).
  * *n_bytes receives the size of the array.  AUGX_E_ARG: the batch has not been decoded, the piece has no such plane (plane must be 0
  * for the arrays without planes), the model has no such array (UFX, UCNT: dense kernels only), or cap_bytes < *n_bytes */
 enum { AUGX_PREP_CODE = 0, AUGX_PREP_CNT, AUGX_PREP_NSM, AUGX_PREP_GCRAW, AUGX_PREP_GCPLANE, AUGX_PREP_FX, AUGX_PREP_SIG, AUGX_PREP_GATE,
-       AUGX_PREP_PLSR, AUGX_PREP_UFX, AUGX_PREP_UCNT, AUGX_PREP_CLS, AUGX_PREP_NPLANES, AUGX_PREP_PLANECLS, AUGX_PREP_LISTCNT, AUGX_PREP_N };
+       AUGX_PREP_PLSR, AUGX_PREP_UFX, AUGX_PREP_UCNT, AUGX_PREP_CLS, AUGX_PREP_NPLANES, AUGX_PREP_PLANECLS, AUGX_PREP_LISTCNT, AUGX_PREP_BPCHAIN,
+       AUGX_PREP_BPD, AUGX_PREP_N };
 int augx_batch_prep(augx_decoder *d, augx_batch *b, int piece, int which, int plane, void *out, int64_t cap_bytes, int64_t *n_bytes);
+/* test hook, as augx_batch_prep (after augx_batch_sync; no kernel is launched): the near ties the back-trace of the last decode counted on
+ * the path of every piece, out[n] (0 for a piece whose status is not 0).  AUGX_E_ARG when the batch was created while the decoder did not
+ * count near ties, or has not been decoded.  Reading them does not change the sums of augx_decoder_near_ties */
+int augx_batch_near_ties(augx_decoder *d, augx_batch *b, int32_t *out /* [n] */);
 /* test hooks: what the replays of the reference's call-history caches (pieces with several GC classes) did in the last
  * augx_batch_decode or augx_batch_forward of the batch.  Only valid on a decoder created with AUGX_DEBUG_CELLS=1 (another decoder keeps
  * nothing); no kernel is launched, nothing is changed.

@@ -86,6 +86,25 @@ struct Twin {
     std::vector<int> nsF, nsR;              // nearestStopForward / Reverse
     std::vector<double> V;                  // [n][S]
     std::vector<int32_t> bpS, bpE;          // back pointers: pred state, endOfPred
+    bool wantR2 = false;                    // nearTies (below): keep ...
+    // of one cell of a variable-length state: the largest candidate that is not the winner (value, ancestor, predecessor end, exon length),
+    // the exon length of the winner, the number of live candidates and whether two of them share a predecessor end
+    struct RunnerUp {
+        double v = -std::numeric_limits<double>::infinity();
+        int a = -1, e = 0, len = 0, winLen = 0, n = 0, lastE = 0, dup = 0;
+        void seen(int eop) { n++; if (n > 1 && eop == lastE) dup = 1; lastE = eop; }
+        void demote(double best, int ba, int be) { v = best; a = ba; e = be; len = winLen; } // (the winner so far becomes the runner-up)
+        void offer(double val, int a2, int eop, int len2) { if (val > v) { v = val; a = a2; e = eop; len = len2; } }
+    };
+    void keepRunnerUp(int j, int s, const RunnerUp &ru, int ba, int be) {
+        const size_t c = (size_t)j * S + s;
+        R2[c] = ru.v; R2n[c] = ru.n; R2len[2 * c] = ru.len; R2len[2 * c + 1] = ru.winLen;
+        R2same[c] = (ru.v > -std::numeric_limits<double>::infinity() && ru.e == be && ru.a != ba ? 1 : 0) | (ru.dup ? 2 : 0);
+    }
+    std::vector<int32_t> R2len;             // ... [n][S][2] the exon lengths of the runner-up and of the winner (coding exons; else 0) ...
+    std::vector<int32_t> R2n;               // ... the live candidates (predecessor end, ancestor) of the cell ...
+    std::vector<uint8_t> R2same;            // ... whether the runner-up shares the winner's predecessor end and differs in the ancestor ...
+    std::vector<double> R2;                 // ... [n][S] for the cells of the variable-length states: the largest candidate other than the winner
 
     Twin(const augx_tables &tt, const char *seq, int len) : t(tt), n(len) {
         S = t.S; k = t.k; NP = 1 << (2 * (k + 1));
@@ -633,6 +652,7 @@ struct Twin {
             startMin = ORFleft <= 0 ? 0 : ORFleft + g.ipo;
             if (startMax > j + g.bpl) startMax = j + g.bpl;
         }
+        RunnerUp ru; // (bookkeeping for nearTies below: it reads the candidates, the recurrence does not read it)
         double best = NINF;
         int ba = -1, be = 0;
         for (int bs = startMax; bs >= startMin; bs--) {
@@ -650,9 +670,12 @@ struct Twin {
                 if (!ok) continue;
                 double te = (lnT(c, a, s) + endP) + nep;
                 double val = pv + te;
-                if (val > best) { best = val; ba = a; be = eop; }
+                ru.seen(eop);
+                if (val > best) { ru.demote(best, ba, be); best = val; ba = a; be = eop; ru.winLen = len; }
+                else ru.offer(val, a, eop, len);
             }
         }
+        if (best > NINF && !R2.empty()) keepRunnerUp(j, s, ru, ba, be);
         if (best > NINF) { Vat(j, s) = best; bpS[(size_t)j * S + s] = ba; bpE[(size_t)j * S + s] = be; }
     }
 
@@ -665,6 +688,7 @@ struct Twin {
         ClassArrays &A = ca[c];
         const int dStateLen = t.d - 2 - t.De - t.As - 2 - t.U;
         const int dssWhole = t.Ds + 2 + t.De, assWhole = t.As + 2 + t.Ae;
+        RunnerUp ru; // (bookkeeping for nearTies below: it reads the candidates, the recurrence does not read it)
         double best = NINF;
         int ba = -1, be = 0;
         if (kind == AUGX_K_LESSD || kind == AUGX_K_RLESSD) {
@@ -720,9 +744,12 @@ struct Twin {
                     double pv = Vat(eop, a);
                     if (pv == NINF) continue;
                     double val = pv + (lnT(c, a, s) + emi);
-                    if (val > best) { best = val; ba = a; be = eop; }
+                    ru.seen(eop);
+                if (val > best) { ru.demote(best, ba, be); best = val; ba = a; be = eop; }
+                    else ru.offer(val, a, eop, 0);
                 }
             }
+            if (best > NINF && !R2.empty()) keepRunnerUp(j, s, ru, ba, be);
         } else {
             int eop;
             double emi;
@@ -965,6 +992,7 @@ struct Twin {
         const int W = t.W, U = t.U, up = t.tss_upwin, te = t.tss_end, dc = t.d_polyasig_cleavage, bl = t.aataaa_boxlen;
         const int assWhole = t.As + 2 + t.Ae, dssWhole = t.Ds + 2 + t.De;
         const int ML = t.utr_max_exon_len, M3S = t.utr_max3single, M3T = t.utr_max3term;
+        RunnerUp ru; // (bookkeeping for nearTies below: it reads the candidates, the recurrence does not read it)
         double best = NINF;
         int ba = -1, be = 0;
         if (kind == AUGX_K_UTR5INTRONVAR || kind == AUGX_K_UTR3INTRONVAR || kind == AUGX_K_RUTR5INTRONVAR || kind == AUGX_K_RUTR3INTRONVAR)
@@ -1156,23 +1184,144 @@ struct Twin {
                 if (pv == NINF) continue;
                 double val = pv + (lnT(c, a, s) + emi);
                 if (checkF) { checkOut = lse(checkOut, val); continue; }
-                if (val > best) { best = val; ba = a; be = eop; }
+                ru.seen(eop);
+                if (val > best) { ru.demote(best, ba, be); best = val; ba = a; be = eop; }
+                else ru.offer(val, a, eop, 0);
             }
         }
         if (checkF) return;
+        if (best > NINF && !R2.empty()) keepRunnerUp(j, s, ru, ba, be);
         if (best > NINF) { Vat(j, s) = best; bpS[(size_t)j * S + s] = ba; bpE[(size_t)j * S + s] = be; }
+    }
+
+    // ------------------------------------------------------------------------------------------
+    // Near ties: the definition of DESIGN.md 6 ("near-ties"), restated from that text over the finished matrix V, the back pointers
+    // and the model tables -- what the device's counter (augx_decoder_count_near_ties) has to report.  The margin of a decision is
+    // winner - runner-up (+inf: there is no live runner-up); a decision is a near tie when its margin is below the threshold.
+    // ------------------------------------------------------------------------------------------
+    static bool tieChainKind(int kind) {
+        return kind == AUGX_K_IGENIC || kind == AUGX_K_GEOMETRIC || kind == AUGX_K_RGEOMETRIC || kind == AUGX_K_UTR5INTRON ||
+               kind == AUGX_K_UTR3INTRON || kind == AUGX_K_RUTR5INTRON || kind == AUGX_K_RUTR3INTRON;
+    }
+    static bool tieVarKind(int kind) { // exon kinds, short introns, UTR exon kinds: the states whose cells take a maximum over predecessor ends
+        if (kind <= AUGX_K_RTERMINAL && kind != AUGX_K_IGENIC) return true;
+        if (kind == AUGX_K_LESSD || kind == AUGX_K_RLESSD) return true;
+        return kind > AUGX_K_RLONGASS && !tieChainKind(kind) && kind != AUGX_K_UTR5INTRONVAR && kind != AUGX_K_UTR3INTRONVAR &&
+               kind != AUGX_K_RUTR5INTRONVAR && kind != AUGX_K_RUTR3INTRONVAR;
+    }
+    // the ways into chain cell (j, s), one per ancestor in the order of anc[s]: V[j-1][a] + (ln T + emission), -inf where V[j-1][a] is
+    bool anyNucleotide = true;
+    void chainWays(int s, int j, double *v) const {
+        const int kind = t.state_kind[s], c = cls[j];
+        const double e = (kind == AUGX_K_IGENIC ? eIg(c, j) : (kind == AUGX_K_GEOMETRIC || kind == AUGX_K_RGEOMETRIC) ? eIn(c, j) : eUin(c, j)) + softB(j);
+        for (int ai = 0; ai < t.n_anc[s]; ai++) {
+            const int a = t.anc[s][ai];
+            const double pv = V[(size_t)(j - 1) * S + a];
+            v[ai] = pv == NINF ? NINF : pv + (lnT(c, a, s) + e);
+        }
+    }
+    // Trellis family (kernels.h:2297-2310, chainPass): three values -- the best way in from an ancestor listed before s itself in anc[s],
+    // staying, the best way in from an ancestor listed after it; the winner is taken with strict '>' in that order; the margin is
+    // winner - the larger of the two losers
+    double marginTrellis(int s, const double *v, int *winner) const {
+        const int na = t.n_anc[s];
+        int self = -1;
+        for (int ai = 0; ai < na; ai++) if (t.anc[s][ai] == s) self = ai;
+        double g[3] = {NINF, NINF, NINF};
+        int gi[3] = {-1, self, -1};
+        for (int ai = 0; ai < na; ai++) {
+            const int grp = ai < self ? 0 : ai == self ? 1 : 2;
+            if (v[ai] > g[grp]) { g[grp] = v[ai]; gi[grp] = ai; }
+        }
+        int w = 0;
+        if (g[1] > g[w]) w = 1;
+        if (g[2] > g[w]) w = 2;
+        *winner = gi[w];
+        double loser = NINF;
+        for (int q = 0; q < 3; q++) if (q != w && g[q] > loser) loser = g[q];
+        return loser > NINF ? g[w] - loser : std::numeric_limits<double>::infinity();
+    }
+    // Dense family (dense.h:1037-1091, chainRun / chainRunSelf after chainOthers): the chain states come in two stages -- the geometric
+    // intron states, and igenic with the UTR intron states.  The candidates of the runner-up are the best way in from outside the stage
+    // of s and every chain ancestor of the stage of s individually; the margin is the largest - the second largest of them (equal values
+    // are two candidates), and the cell has one only when the index of the winning ancestor in anc[s] is below 8
+    double marginDense(int s, const double *v, int *winner) const {
+        const int na = t.n_anc[s];
+        auto early = [](int kind) { return kind == AUGX_K_GEOMETRIC || kind == AUGX_K_RGEOMETRIC; };
+        const bool se = early(t.state_kind[s]);
+        double oth = NINF, f = NINF, f2 = NINF;
+        int w = -1;
+        for (int ai = 0; ai < na; ai++) { // the winner: the first of the largest, as the back pointer
+            if (v[ai] > f) { f = v[ai]; w = ai; }
+            const int ka = t.state_kind[t.anc[s][ai]];
+            if (!(tieChainKind(ka) && early(ka) == se) && v[ai] > oth) oth = v[ai];
+        }
+        *winner = w;
+        f = NINF;
+        auto offer = [&](double x) { if (x > f) { f2 = f; f = x; } else if (x > f2) f2 = x; };
+        offer(oth);
+        for (int ai = 0; ai < na; ai++) {
+            const int ka = t.state_kind[t.anc[s][ai]];
+            if (tieChainKind(ka) && early(ka) == se) offer(v[ai]);
+        }
+        return (w >= 0 && w < 8 && f2 > NINF) ? f - f2 : std::numeric_limits<double>::infinity();
+    }
+    // The full definition (no kernel computes it): the runner-up is the largest way in over ALL ancestors other than the winner, no index guard
+    double marginFull(int s, const double *v) const {
+        double f = NINF, f2 = NINF;
+        for (int ai = 0; ai < t.n_anc[s]; ai++) { if (v[ai] > f) { f2 = f; f = v[ai]; } else if (v[ai] > f2) f2 = v[ai]; }
+        return f2 > NINF ? f - f2 : std::numeric_limits<double>::infinity();
+    }
+    struct TieRec { int32_t base, state, rule; double margin, marginFull; int32_t nCand, sameEnd, ruLen, winLen; };
+    int finalState = -1;
+    // family 0: trellis kernels, 1: dense kernels.  mk / mf [n][S]: the margin of every live chain cell under the family's rule / the
+    // full definition (NaN: not a live chain cell).  recs: what the count of the piece is made of, 3' to 5' as the back-trace meets it --
+    // every chain cell of the path's chain runs, from the entry cell of the run (or base 1) up to its top (kernels.h:3459-3471,
+    // dense.h:1434-1440; rule 0: the entry cell, 1: another cell of the run), and every variable-length element (rule 2: exon kinds,
+    // lessD, UTR exon kinds; kernels.h:3493-3532, dense.h:1456-1479, 1490-1518), whose margin is best - the largest live candidate
+    // (predecessor end, ancestor) other than the winner and which is counted when 0 < margin < eps.  Fixed-lag states are never counted.
+    mutable long winnerMismatch = 0;
+    void nearTies(int family, std::vector<double> &mk, std::vector<double> &mf, std::vector<TieRec> &recs) const {
+        const double nan = std::numeric_limits<double>::quiet_NaN(), inf = std::numeric_limits<double>::infinity();
+        mk.assign((size_t)n * S, nan); mf.assign((size_t)n * S, nan);
+        std::vector<double> v((size_t)AUGX_MAX_ANC + 1);
+        for (int j = 1; j < n; j++)
+            for (int s = 0; s < S; s++) {
+                if (!t.reachable[s] || !tieChainKind(t.state_kind[s]) || !(V[(size_t)j * S + s] > NINF)) continue;
+                if (!anyNucleotide) { mk[(size_t)j * S + s] = mf[(size_t)j * S + s] = inf; continue; } // (a piece of N only: no decision is made, src/namgene.cc:205-226)
+                chainWays(s, j, v.data());
+                int w;
+                mk[(size_t)j * S + s] = family == 0 ? marginTrellis(s, v.data(), &w) : marginDense(s, v.data(), &w);
+                if (w < 0 || t.anc[s][w] != bpS[(size_t)j * S + s]) winnerMismatch++; // (the rule's winner is the decode's own back pointer)
+                mf[(size_t)j * S + s] = marginFull(s, v.data());
+            }
+        recs.clear();
+        int state = finalState, base = n - 1;
+        while (state >= 0 && base > 0) {
+            const int a = bpS[(size_t)base * S + state], e = bpE[(size_t)base * S + state], kind = t.state_kind[state];
+            if (a < 0) break;
+            if (tieChainKind(kind)) recs.push_back({base, state, (a != state || base == 1) ? 0 : 1, mk[(size_t)base * S + state], mf[(size_t)base * S + state], 0, 0, 0, 0});
+            else if (tieVarKind(kind)) {
+                const double r2 = R2[(size_t)base * S + state];
+                const double m = r2 > NINF ? V[(size_t)base * S + state] - r2 : inf;
+                recs.push_back({base, state, 2, m, m, R2n[(size_t)base * S + state], R2same[(size_t)base * S + state], R2len[2 * ((size_t)base * S + state)], R2len[2 * ((size_t)base * S + state) + 1]});
+            }
+            base = e; state = a;
+        }
     }
 
     int run(int init_kind, int term_kind, double *lnv, std::vector<augx_state> &path) {
         V.assign((size_t)n * S, NINF);
         bpS.assign((size_t)n * S, -1);
         bpE.assign((size_t)n * S, -1);
+        if (wantR2) { R2.assign((size_t)n * S, NINF); R2n.assign((size_t)n * S, 0); R2same.assign((size_t)n * S, 0); R2len.assign((size_t)n * S * 2, 0); }
         for (int i = 0; i < S; i++) // reference NAMGene::setStatesInitialProbs, src/namgene.cc:144-150
             Vat(0, i) = init_kind == 0 ? t.ln_init[i] : (i == t.synch_state ? 0.0 : NINF);
         computeStairs();
         buildORF();
         bool anyNuc = false;
         for (int i = 0; i < n; i++) anyNuc |= code[i] < 4;
+        anyNucleotide = anyNuc;
         if (!anyNuc) { // reference src/namgene.cc:205-226
             for (int j = 1; j < n; j++) {
                 Vat(j, t.synch_state) = Vat(j - 1, t.synch_state) - t.ln4;
@@ -1212,6 +1361,7 @@ struct Twin {
             if (v > maxV) { maxV = v; state = i; }
         }
         *lnv = maxV;
+        finalState = state;
         path.clear();
         if (state < 0) return AUGX_E_NOPATH;
         int base = n - 1;
@@ -1287,6 +1437,91 @@ int twin_decode(const augx_tables *t, const char *seq, int64_t len, int init_kin
     if (n_states) *n_states = (int32_t)path.size();
     if (states_out)
         for (int32_t i = 0; i < cap && i < (int32_t)path.size(); i++) states_out[i] = path[i];
+    return rc;
+}
+/* the reachable single-base chain states of the model in the order of the state index (the order of the bytes of BatchView::bpChain) */
+int twin_chain_states(const augx_tables *t, int32_t *out /* [S] */) {
+    int k = 0;
+    for (int s = 0; t && s < t->S; s++)
+        if (t->reachable[s] && Twin::tieChainKind(t->state_kind[s])) out[k++] = s;
+    return k;
+}
+/* per state: 0 not reachable, 1 single-base chain state, 2 variable-length state (its elements on a path can be counted), 3 fixed-lag state;
+ * kind_out (may be NULL): the AUGX_K_* kind of every state */
+void twin_tie_classes(const augx_tables *t, int32_t *out /* [S] */, int32_t *kind_out /* [S] */) {
+    for (int s = 0; s < t->S; s++) {
+        const int k = t->state_kind[s];
+        out[s] = !t->reachable[s] ? 0 : Twin::tieChainKind(k) ? 1 : Twin::tieVarKind(k) ? 2 : 3;
+        if (kind_out) kind_out[s] = k;
+    }
+}
+/* A copy of the tables in which entry `len` of the length distribution of the coding exons of kind `kind` (single, initial, internal,
+ * terminal, either strand) is raised by delta; everything else is shared with t, which must outlive the copy.  With delta = the margin of
+ * an element and len = the exon length of its runner-up, runner-up and winner are bit-equal: an exact tie reached through the model
+ * (tests/test_emu_ties.py).  NULL for another kind or a length outside the table; free with twin_tables_free */
+struct TablesCopy { augx_tables t; std::vector<double> len; };
+const augx_tables *twin_tables_bump_exon_length(const augx_tables *t, int kind, int len, double delta) {
+    if (!t || len < 0 || len > t->max_exon_len) return nullptr;
+    const double *src = (kind == AUGX_K_SINGLE || kind == AUGX_K_RSINGLE) ? t->len_single : (kind == AUGX_K_INITIAL || kind == AUGX_K_RINITIAL) ? t->len_initial
+                        : (kind == AUGX_K_INTERNAL || kind == AUGX_K_RINTERNAL) ? t->len_internal : (kind == AUGX_K_TERMINAL || kind == AUGX_K_RTERMINAL) ? t->len_terminal : nullptr;
+    if (!src) return nullptr;
+    TablesCopy *c = new TablesCopy{*t, std::vector<double>(src, src + t->max_exon_len + 1)};
+    c->len[(size_t)len] += delta;
+    if (src == t->len_single) c->t.len_single = c->len.data();
+    else if (src == t->len_initial) c->t.len_initial = c->len.data();
+    else if (src == t->len_internal) c->t.len_internal = c->len.data();
+    else c->t.len_terminal = c->len.data();
+    return &c->t;
+}
+void twin_tables_free(const augx_tables *t) { delete reinterpret_cast<TablesCopy *>(const_cast<augx_tables *>(t)); }
+/* the ancestors of state s in the order of anc[s]; returns how many */
+int twin_ancestors(const augx_tables *t, int s, int32_t *out /* [AUGX_MAX_ANC] */) {
+    for (int i = 0; i < t->n_anc[s]; i++) out[i] = t->anc[s][i];
+    return t->n_anc[s];
+}
+/* Near ties of one piece under the definition of DESIGN.md 6 (Twin::nearTies above); family 0: the trellis kernels, 1: the dense kernels.
+ * margin / margin_full [len][S] (may be NULL): winner - runner-up of every live chain cell under the family's rule / the full definition
+ *   (+inf: no runner-up, NaN: not a live chain cell); a cell is flagged when its margin is below eps
+ * list [cap][7] (base, state, rule: 0 entry cell of a chain run, 1 another cell of it, 2 variable-length element; for rule 2 the number of live
+ *   candidates (predecessor end, ancestor) of the cell, and bit 0: the runner-up shares the winner's predecessor end and differs in the ancestor,
+ *   bit 1: some two live candidates of the cell share a predecessor end; the exon length of the runner-up and of the winner, coding exons) and list_margin [cap][2]
+ *   (family's rule, full definition): what the count is made of, 3' to 5'; *n_list: how many there are
+ * *count / *count_full: near ties on the path at threshold eps; 0 for a piece whose decode fails
+ * V_out, states_out, cap_states, n_states, ln_viterbi: as twin_decode (any may be NULL).  Returns the status of the decode */
+int twin_near_ties(const augx_tables *t, const char *seq, int64_t len, int init_kind, int term_kind, int family, double eps,
+                   double *margin, double *margin_full, int32_t *list, double *list_margin, int64_t cap, int64_t *n_list,
+                   int64_t *count, int64_t *count_full, double *V_out, augx_state *states_out, int32_t cap_states, int32_t *n_states,
+                   double *ln_viterbi) {
+    if (!t || !seq || len < 1 || family < 0 || family > 1 || !(eps > 0.0)) return AUGX_E_ARG;
+    Twin tw(*t, seq, (int)len);
+    tw.wantR2 = true;
+    std::vector<augx_state> path;
+    double lnv;
+    const int rc = tw.run(init_kind, term_kind, &lnv, path);
+    if (ln_viterbi) *ln_viterbi = lnv;
+    if (V_out) memcpy(V_out, tw.V.data(), sizeof(double) * (size_t)len * t->S);
+    if (n_states) *n_states = (int32_t)path.size();
+    for (int32_t i = 0; states_out && i < cap_states && i < (int32_t)path.size(); i++) states_out[i] = path[i];
+    std::vector<double> mk, mf;
+    std::vector<Twin::TieRec> recs;
+    tw.nearTies(family, mk, mf, recs);
+    if (rc != 0) recs.clear();
+    if (margin) memcpy(margin, mk.data(), sizeof(double) * mk.size());
+    if (margin_full) memcpy(margin_full, mf.data(), sizeof(double) * mf.size());
+    int64_t c = 0, cf = 0;
+    for (size_t i = 0; i < recs.size(); i++) {
+        const Twin::TieRec &r = recs[i];
+        if (r.rule == 2) { const int hit = r.margin < eps && r.margin != 0.0; c += hit; cf += hit; } // (an exact tie of a variable-length element is not counted)
+        else { c += r.margin < eps; cf += r.marginFull < eps; }                                       // (an exact tie of a chain cell is)
+        if (list && list_margin && (int64_t)i < cap) {
+            list[i * 7] = r.base; list[i * 7 + 1] = r.state; list[i * 7 + 2] = r.rule; list[i * 7 + 3] = r.nCand; list[i * 7 + 4] = r.sameEnd; list[i * 7 + 5] = r.ruLen; list[i * 7 + 6] = r.winLen;
+            list_margin[i * 2] = r.margin; list_margin[i * 2 + 1] = r.marginFull;
+        }
+    }
+    if (n_list) *n_list = (int64_t)recs.size();
+    if (count) *count = c;
+    if (count_full) *count_full = cf;
+    if (tw.winnerMismatch) return AUGX_E_ARG - 1000; // (cannot happen: the winner of a family's rule differs from the back pointer of the cell)
     return rc;
 }
 }

@@ -10,6 +10,7 @@
 #include <cstring>
 #include <cstdlib>
 #include <chrono>
+#include <array>
 #include <vector>
 #include <memory>
 #include <functional>
@@ -20,6 +21,8 @@
 #include "../../augustus_amd/csrc/device/sampler.h"
 #include "../../augustus_amd/csrc/device/snipmemo.h"
 static std::vector<int32_t> g_nearTies; // near ties on the chosen path of every piece of the last decode (dp.h: AUGX_NEAR_TIE)
+static std::vector<std::array<int32_t, 5>> g_segStops; // per segment of the last trellis decode: piece, first tile, end tile, seg_stop, seg_stop2
+static double g_nearTieEps = augx::dev::AUGX_NEAR_TIE; // the threshold of the decodes from now on (emu_set_near_tie_eps; augx_decoder_set_near_tie_eps)
 
 using namespace augx::dev;
 
@@ -52,6 +55,8 @@ struct PrepSnap {
     std::vector<uint64_t> fx, gate, ufx;
     std::vector<double> sig, plsR;
     std::vector<int32_t> cls, nPlanes, planeCls, listCnt, runs;
+    std::vector<uint8_t> bpChain, bpD; // the back pointers of the chain states as the decode left them (after the back-trace; emu_decode)
+    int S = 0;
 };
 bool g_keepPrep = false;
 PrepSnap g_prep;
@@ -207,6 +212,7 @@ static int emu_decode_dense(const augx_tables *t, const augx_piece *pieces, int 
     B.pathRec = (int32_t *)za(Z.pathCap * 3, 4);
     g_nearTies.assign((size_t)n, 0);
     B.nearTie = g_nearTies.data();
+    B.nearTieEps = g_nearTieEps;
     for (int64_t g = 0; g < B.N; g++) k1Encode(B, g);
     for (int64_t g = 0; g < B.N; g++) k1SiteTerms(T, B, g);
     scanFields<false>(B.cnt, NCNT, L);
@@ -410,6 +416,7 @@ static int emu_decode_dense(const augx_tables *t, const augx_piece *pieces, int 
         }
         denseBacktracePiece(T, B, p);
     }
+    if (g_prep.have) { g_prep.S = t->S; g_prep.bpD.assign(B.bpD, B.bpD + Z.N * t->S); }
     if (fwd_out) {
         B.fwd = (double *)za(Z.N * t->S, 8);
         std::vector<double> lnF(n);
@@ -528,8 +535,9 @@ void emu_model_dims(const augx_tables *t, long long *out) {
     out[0] = t->d; out[1] = t->max_exon_len; out[2] = t->W; out[3] = D.dStateLen; out[4] = t->n_classes; out[5] = forwardCellCandidates(*t);
 }
 // the build-time windows of the trellis (dp.h: AUGX_ITEM_CAP, AUGX_LIST_WIN, AUGX_VIG_WIN), what trellisItems and forwardPiece derive
-// from the build (LIST_AHEAD, NTW), and the terms of 1.0 a fixed-point forward sum holds (dp.h: FWD_SUM_TERMS)
-void emu_trellis_windows(int *out) { out[0] = ITEM_CAP; out[1] = LIST_WIN; out[2] = VIG_WIN; out[3] = LIST_AHEAD; out[4] = NT - WAVE; out[5] = (int)FWD_SUM_TERMS; }
+// from the build (LIST_AHEAD, NTW), the terms of 1.0 a fixed-point forward sum holds (dp.h: FWD_SUM_TERMS), and the rounds of the back-traces
+void emu_trellis_windows(int *out) { out[0] = ITEM_CAP; out[1] = LIST_WIN; out[2] = VIG_WIN; out[3] = LIST_AHEAD; out[4] = NT - WAVE; out[5] = (int)FWD_SUM_TERMS;
+                                      out[6] = BT_ROUND; out[7] = 4 * WAVE; } // ([6], [7]: bases of a chain run per round of the back-trace, kernels.h: BT_ROUND / dense.h: denseBacktracePiece)
 // block size of the candidate / trellis kernels that a decode of this model takes (layout.h; AUGX_BLK applies), -1: unsupported
 int emu_block_size(const augx_tables *t) {
     try { return chooseBlockSize(*t); } catch (std::exception &) { return -1; }
@@ -573,12 +581,22 @@ int emu_prep(int p, int which, int plane, void *out, int64_t cap_bytes, int64_t 
     case AUGX_PREP_NPLANES: perPiece(P.nPlanes.data(), 1); break;
     case AUGX_PREP_PLANECLS: perPiece(P.planeCls.data(), MAXPL); break;
     case AUGX_PREP_LISTCNT: perPiece(P.listCnt.data(), 1); break;
+    case AUGX_PREP_BPCHAIN: if (!P.bpChain.empty()) basesOf(P.bpChain.data(), 1, 8, len); break;
+    case AUGX_PREP_BPD: if (!P.bpD.empty()) basesOf(P.bpD.data(), 1, P.S, len); break;
     }
     if (!src) return AUGX_E_ARG;
     *n_bytes = bytes;
     if (!out || cap_bytes < bytes) return AUGX_E_ARG;
     memcpy(out, src, (size_t)bytes);
     return 0;
+}
+// as augx_decoder_set_near_tie_eps: the threshold of the decodes from now on; refuses values that are not finite and positive
+int emu_set_near_tie_eps(double eps) { if (!std::isfinite(eps) || !(eps > 0.0)) return AUGX_E_ARG; g_nearTieEps = eps; return 0; }
+// the segments of the last decode by the trellis kernels, [cap][5]: piece, first tile, end tile (tiles of 64 bases), and where the fix-up of the
+// segment and its continuation stopped, as augx_batch_plan gives seg_stop / seg_stop2 (include/augx.h); returns the number of segments
+int emu_seg_stops(int32_t *out, int cap) {
+    for (int i = 0; i < (int)g_segStops.size() && i < cap; i++) for (int k = 0; k < 5; k++) out[i * 5 + k] = g_segStops[(size_t)i][k];
+    return (int)g_segStops.size();
 }
 int emu_near_ties(int p) { return p >= 0 && p < (int)g_nearTies.size() ? g_nearTies[p] : -1; }
 // values of the TSS window at base 0 of the pieces of the NEXT emu_decode, [n][2] forward / reverse, NaN: the piece's own (n = 0: none)
@@ -706,6 +724,7 @@ int emu_decode(const augx_tables *t, const augx_piece *pieces, int n, double *ln
     B.pathRec = zalloc<int32_t>(Z.pathCap * 3);
     g_nearTies.assign((size_t)n, 0);
     B.nearTie = g_nearTies.data();
+    B.nearTieEps = g_nearTieEps;
 
     // ---- K1
     for (int64_t g = 0; g < B.N; g++) k1Encode(B, g);
@@ -893,6 +912,8 @@ int emu_decode(const augx_tables *t, const augx_piece *pieces, int n, double *ln
 #undef EMU_TRELLIS
     int nGaveUp = 0;
     for (int sg = 0; sg < B.nSegs; sg++) nGaveUp += segStop[sg] <= -2;
+    g_segStops.clear(); // (emu_seg_stops: the plan of the segments and where fix-ups and continuations stopped, as augx_batch_plan hands them out)
+    for (int sg = 0; sg < B.nSegs; sg++) g_segStops.push_back({plan.segs[sg].piece, plan.segs[sg].t0, plan.segs[sg].t1, segStop[sg], segStop2[sg]});
     if (getenv("AUGX_EMU_STATS")) {
         fprintf(stderr, "emu stats: trellis candidates read back from HBM: igenic %lld, list %lld, in %lld chunks of 64\n", g_emuSlowVig, g_emuSlowList, g_emuItemWaves);
 
@@ -904,6 +925,7 @@ int emu_decode(const augx_tables *t, const augx_piece *pieces, int n, double *ln
         segFinalizePiece(B, p);
         backtracePiece(T, B, p);
     }
+    if (g_prep.have) g_prep.bpChain.assign(B.bpChain, B.bpChain + Z.N * 8);
     delete lds;
     if (fwd_out) { // ---- forward algorithm (posterior sampling), after the Viterbi decode
         B.fwd = zalloc<double>(Z.N * t->S);

@@ -124,6 +124,124 @@ def twin_decode(tables_ptr, seq, S, cells=False, init_kind=0, term_kind=0, cache
     return rc, lnv.value, path, V, gc
 
 
+def twin_chain_states(tables_ptr, S):
+    """the reachable single-base chain states of the model in the order of the state index: byte c of a bpChain record is state [c]"""
+    out = np.zeros(S, dtype=np.int32)
+    k = twin().twin_chain_states(tables_ptr, out.ctypes.data_as(ctypes.c_void_p))
+    return [int(x) for x in out[:k]]
+
+
+def twin_tie_classes(tables_ptr, S):
+    """(class, kind) of every state: class 0 not reachable, 1 single-base chain state, 2 variable-length state (exon kinds, lessD, UTR exon
+    kinds: its elements on a path can be counted as near ties), 3 fixed-lag state (never counted); kind: AUGX_K_*"""
+    c, k = np.zeros(S, dtype=np.int32), np.zeros(S, dtype=np.int32)
+    twin().twin_tie_classes(tables_ptr, c.ctypes.data_as(ctypes.c_void_p), k.ctypes.data_as(ctypes.c_void_p))
+    return [int(x) for x in c], [int(x) for x in k]
+
+
+class TwinTies:
+    """what oracle/ghmm_twin.cc: twin_near_ties says about one piece (the definition of DESIGN.md 6, "near-ties"):
+    rc, lnv, path, V as twin_decode; margin / margin_full [n, S]: winner - runner-up of every live chain cell under the rule of the kernel
+    family / the full definition (+inf: no runner-up, NaN: not a live chain cell); items: [(base, state, rule, margin, margin_full)], what the
+    count of the piece is made of, 3' to 5' (rule 0: entry cell of a chain run, 1: another cell of it, 2: variable-length element)"""
+
+    def __init__(self, tables_ptr, seq, S, family, init_kind=0, term_kind=0, cache=None):
+        n = len(seq)
+        if cache is None:
+            cache = os.environ.get("AUGX_EXACT_MULTICLASS", "1") != "0"
+        twin().twin_set_snippet_cache(1 if cache else 0)
+        self.n, self.S, self.family = n, S, family
+        self.all_n = not any(c in "ACGTacgt" for c in (seq if isinstance(seq, str) else seq.decode()))  # (a piece without a nucleotide)
+        self.V, self.margin, self.margin_full = np.empty((n, S)), np.empty((n, S)), np.empty((n, S))
+        cap, pcap = n + 16, max(1024, n // 4 + 16)
+        lst, lm = np.zeros((cap, 7), dtype=np.int32), np.zeros((cap, 2))
+        sts = (_St * pcap)()
+        nl, c, cf, ns, lnv = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int32(), ctypes.c_double()
+        T = twin()
+        T.twin_near_ties.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double] + \
+                                    [ctypes.c_void_p] * 4 + [ctypes.c_int64] + [ctypes.POINTER(ctypes.c_int64)] * 3 + \
+                                    [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double)]
+        self.rc = T.twin_near_ties(tables_ptr, seq.encode() if isinstance(seq, str) else seq, n, init_kind, term_kind, family, 1.0,
+                                   self.margin.ctypes.data_as(ctypes.c_void_p), self.margin_full.ctypes.data_as(ctypes.c_void_p),
+                                   lst.ctypes.data_as(ctypes.c_void_p), lm.ctypes.data_as(ctypes.c_void_p), cap, ctypes.byref(nl), ctypes.byref(c), ctypes.byref(cf),
+                                   self.V.ctypes.data_as(ctypes.c_void_p), sts, pcap, ctypes.byref(ns), ctypes.byref(lnv))
+        assert nl.value <= cap and ns.value <= pcap
+        self.lnv = lnv.value
+        self.path = [(sts[i].begin, sts[i].end, sts[i].state, sts[i].type) for i in range(ns.value)]
+        self.items = [(int(lst[i, 0]), int(lst[i, 1]), int(lst[i, 2]), float(lm[i, 0]), float(lm[i, 1])) for i in range(nl.value)]
+        # (base, state) of a variable-length element -> (live candidates of its cell, the runner-up shares the winner's predecessor end and differs in the ancestor,
+        # some two live candidates of the cell share a predecessor end, exon length of the runner-up, of the winner -- coding exons, else 0)
+        self.cands = {(int(lst[i, 0]), int(lst[i, 1])): (int(lst[i, 3]), bool(lst[i, 4] & 1), bool(lst[i, 4] & 2), int(lst[i, 5]), int(lst[i, 6])) for i in range(nl.value) if lst[i, 2] == 2}
+        assert self.counts(1.0) == (c.value, cf.value)  # (the twin's own sums at the threshold it was called with)
+
+    def counts(self, eps):
+        """(count, count under the full definition) of the piece at threshold eps: the flagged chain cells of the path's chain runs and
+        the variable-length elements of the path with 0 < margin < eps (an exact tie of a variable-length element is not counted)"""
+        c = sum(1 for _, _, rule, mk, _ in self.items if mk < eps and (rule < 2 or mk != 0.0))
+        cf = sum(1 for _, _, rule, _, mf in self.items if mf < eps and (rule < 2 or mf != 0.0))
+        return c, cf
+
+    def flags(self, eps, full=False):
+        """[n, S] int8: -1 not a live chain cell, 1 flagged at threshold eps, 0 not"""
+        m = self.margin_full if full else self.margin
+        with np.errstate(invalid="ignore"):
+            return np.where(np.isnan(m), -1, (m < eps).astype(np.int8)).astype(np.int8)
+
+
+def chain_flags_of(bytes_, chain_states, S, dense=False):
+    """the near-tie flags a decode left (Batch.prep / emu_prep, "bpChain" [n, 8] or "bpD" [n * S]) in the shape of TwinTies.flags: [n, S]
+    int8, -1: no value (base 0 of a piece holds none), -2: the dense kernels' mark of a piece of N only"""
+    if dense:
+        b = np.asarray(bytes_).reshape(-1, S)
+        out = np.full(b.shape, -1, dtype=np.int8)
+        for s in chain_states:
+            out[:, s] = np.where(b[:, s] == 0xFF, -1, np.where(b[:, s] == 0xFE, -2, (b[:, s] >> 6) & 1))  # (0xFE: a piece of N only)
+    else:
+        b = np.asarray(bytes_).reshape(-1, 8)
+        out = np.full((len(b), S), -1, dtype=np.int8)
+        for c, s in enumerate(chain_states):
+            out[:, s] = np.where(b[:, c] == 0xFF, -1, b[:, c] >> 7)
+    out[0, :] = -1
+    return out
+
+
+class BumpedTables:
+    """the tables of model m with entry `length` of the length distribution of the coding exons of kind `kind` raised by delta (oracle/
+    ghmm_twin.cc: twin_tables_bump_exon_length; everything else is shared with m, which it keeps alive): stands in for a model where twin
+    and emulator take one (tables_ptr, n_states)"""
+
+    def __init__(self, m, kind, length, delta):
+        T = twin()
+        T.twin_tables_bump_exon_length.restype = ctypes.c_void_p
+        T.twin_tables_bump_exon_length.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_double]
+        T.twin_tables_free.argtypes = [ctypes.c_void_p]
+        self.model, self.n_states = m, m.n_states
+        self._p = T.twin_tables_bump_exon_length(m.tables_ptr, kind, length, delta)
+        assert self._p
+
+    @property
+    def tables_ptr(self):
+        return ctypes.c_void_p(self._p)
+
+    def __del__(self):
+        if getattr(self, "_p", None):
+            twin().twin_tables_free(self._p)
+            self._p = None
+
+
+def emu_set_near_tie_eps(eps, lib=None):
+    """the threshold of the near-tie counter for the emulator's decodes from now on (tests/emu/emu.cc; None: the product's)"""
+    E = _emu_of(lib)
+    E.emu_set_near_tie_eps.argtypes = [ctypes.c_double]
+    return E.emu_set_near_tie_eps(2e-7 if eps is None else float(eps))
+
+
+def emu_near_ties(n, lib=None):
+    """near ties the emulator's back-trace counted on the paths of the n pieces of its last decode"""
+    E = _emu_of(lib)
+    return [E.emu_near_ties(i) for i in range(n)]
+
+
 def twin_cache_log(tables_ptr, seq, S, cells=False, init_kind=0, term_kind=0):
     """twin_decode with the restated caches on and their log kept (oracle/ghmm_twin.cc: twin_set_cache_log).  Returns
     (twin_decode's tuple, {(j, s, eop): term} of every short-intron request the SnippetProbs cache answered with another content than
@@ -870,10 +988,11 @@ def emu_trellis_coverage_reset(lib=None):
 
 def emu_trellis_windows(lib=None):
     """the trellis windows the emulator `lib` was built with: {ITEM_CAP, LIST_WIN, VIG_WIN, LIST_AHEAD, NTW} (kernels.h), and
-    FWD_SUM_TERMS, the terms of 1.0 a fixed-point sum of the forward kernels holds (dp.h)"""
+    FWD_SUM_TERMS, the terms of 1.0 a fixed-point sum of the forward kernels holds (dp.h); BT_ROUND / BT_ROUND_DENSE: the bases of a
+    chain run that one round of loads of the back-trace covers (kernels.h: backtracePiece / dense.h: denseBacktracePiece)"""
     out = (ctypes.c_int * 8)()
     _emu_of(lib).emu_trellis_windows(out)
-    return dict(zip(("ITEM_CAP", "LIST_WIN", "VIG_WIN", "LIST_AHEAD", "NTW", "FWD_SUM_TERMS"), out[:6]))
+    return dict(zip(("ITEM_CAP", "LIST_WIN", "VIG_WIN", "LIST_AHEAD", "NTW", "FWD_SUM_TERMS", "BT_ROUND", "BT_ROUND_DENSE"), out[:8]))
 
 
 def revcomp(s):
@@ -1217,3 +1336,281 @@ def assert_terms_equal(got, want, what):
     assert not missing and not extra, (what, "not patched", missing[:5], len(missing), "patched, not in the twin's log", extra[:5], len(extra))
     wrong = [(k, got[k], want[k]) for k in want if got[k] != want[k]]
     assert not wrong, (what, wrong[:5], len(wrong))
+
+
+# ---------------------------------------------------------------------------------------------------
+# the near-tie counter against the twin's definition (tests/test_emu_ties.py, tests/test_gpu_ties.py; DESIGN.md 6 "near-ties")
+# ---------------------------------------------------------------------------------------------------
+TIES_CFGS = {**GOLDEN_CFGS, **GENEMODEL_CFGS, "caenorhabditis": ("caenorhabditis", {"UTR": "off", "sample": "0", "softmasking": "0"}),
+             "maize": ("maize", {"UTR": "off", "sample": "0", "softmasking": "0"})}
+# (configuration, AUGX_BLK or None: the model's own block size)
+TIES_TRELLIS = [("human", None), ("caenorhabditis", None), ("human", "2")]
+TIES_DENSE = [("human_utr", "4"), ("human_utr", "2"), ("fly_utr", "4"), ("human_atleastone", "8"), ("maize", "8")]
+TIES_PRODUCT_EPS = 2e-7  # dp.h: AUGX_NEAR_TIE
+# The large threshold of each configuration, chosen from the twin's margins (DESIGN.md 6 has the flagged share of every record): with it
+# every record named in TIES_ON_PATH has between 1 % and 50 % of the chain cells of its path flagged, which the tests assert
+TIES_EPS = {"human": 20.0, "caenorhabditis": 20.0, "human_utr": 20.0, "fly_utr": 20.0, "human_atleastone": 20.0, "maize": 20.0}
+# a second large threshold for the UTR site-list branch of the dense back-trace: at 20.0 the candidate BEHIND a runner-up that shares the
+# winner's predecessor end lies within the threshold as well, so the count cannot tell whether pass 1 excluded the winner by its end
+# alone; at 12.0 it does on withN (1 % to 50 % of the chain cells of its path are flagged there too, asserted)
+TIES_EPS_SHARED_END = 12.0
+_ties_twin = {}
+
+
+def ties_family(cfg):
+    """0: the configuration is decoded by the trellis kernels, 1: by the dense kernels"""
+    return 1 if cfg in [c for c, _ in TIES_DENSE] else 0
+
+
+def ties_twin(m, cfg, seq, init_kind=0, term_kind=0, tag=None):
+    """TwinTies of one record under configuration cfg, computed once per process (the twin knows neither AUGX_BLK nor the threshold).
+    Follows AUGX_EXACT_MULTICLASS like twin_decode.  tag: names the model m when it is not the one of TIES_CFGS[cfg]"""
+    key = (tag or cfg, seq, init_kind, term_kind, os.environ.get("AUGX_EXACT_MULTICLASS", "1") != "0")
+    if key not in _ties_twin:
+        _ties_twin[key] = TwinTies(m.tables_ptr, seq, m.n_states, ties_family(cfg), init_kind, term_kind)
+    return _ties_twin[key]
+
+
+def ties_share(T, eps):
+    """share of the chain cells on the twin's path that are flagged at threshold eps"""
+    on = [it for it in T.items if it[2] < 2]
+    return sum(1 for it in on if it[3] < eps) / max(1, len(on))
+
+
+def ties_first_diff(flags, T, eps):
+    """None when the flags a decode left ([n, S] as chain_flags_of) equal the twin's for every chain cell of every base >= 1 -- live where
+    the twin's cell is live, flagged where the twin's margin is below eps --, else a text that names the first cell that differs"""
+    want = T.flags(eps)
+    want[0, :] = -1
+    # (-2: the dense kernels' mark of a piece of N only, written for the synch state whether or not its cell is live: no decision, no
+    # flag.  Allowed in a piece without a nucleotide only: anywhere else it is a difference)
+    if T.all_n:
+        flags = np.where((flags == -2) & (want != 1), want, flags)
+    bad = np.argwhere(flags != want)
+    if len(bad) == 0:
+        return None
+    j, s = (int(x) for x in bad[0])
+    return "%d chain cells differ, first at base %d state %d: %d against the twin's %d (margin %r)" % (len(bad), j, s, flags[j, s], want[j, s], T.margin[j, s])
+
+
+K_RSINGLE, K_RTERMINAL, K_UTR5SINGLE = 5, 8, 19  # include/augx.h: AUGX_K_RSINGLE, AUGX_K_RTERMINAL, AUGX_K_UTR5SINGLE (the first UTR kind)
+
+
+def ties_conditions(T, eps, R, chain_states, kinds=None, dense=False):
+    """the shapes the inputs of the near-tie tests are there for, as the TWIN's path and margins show them at threshold eps (R: the bases of
+    a chain run that one round of loads of the back-trace covers).  The in-round distance of a cell of a chain run is (top of the run -
+    base) mod R, as the back-trace walks the run down from its top; in the trellis family the pair of bases at distances 128 j + 2 l and
+    + 1 is load j of lane l.  Returns a set of names:
+      flag_d0 / _d1 / _dR-2 / _dR-1 / _next0: a flagged cell at that in-round distance (next0: distance 0 of the second round) in a run
+        longer than 2 R; noflag_...: an unflagged cell there beside a flagged cell of the same run;
+      entry_flag_d0 / entry_flag_dR-1 / entry_noflag_d0 / entry_noflag_dR-1: a run entered from another state inside the piece whose entry
+        cell is at that in-round distance, flagged / not; entry_flag, entry_noflag: at any distance;
+      run_to_base1: a run that reaches base 1; flag_base1, flag_last_base: a flagged cell on the path at base 1 / the last base of the piece;
+      lane0, lane63: a flagged cell of the path in lane 0 / 63 of a load (dense=True: of a chunk of the dense back-trace's count loop, which
+        goes up from the entry cell; flag_tail_chunk: a flagged cell in its last, partly filled chunk); slot<c>: a flagged cell of the path in chain slot c;
+      cells_slot<c>: a flagged cell anywhere in the matrix in chain slot c; var<state>: a counted variable-length element of that state;
+      var_tie: a variable-length element of the path with an exact tie (margin 0: not counted);
+      with kinds (the AUGX_K_* kind of every state), per branch of the back-trace that takes the arg-max of such an element again -- rec: the
+      candidate records of kCand (coding exons, lessD), utr: the UTR site list (UTR exon kinds; AUGX_K_UTR5SINGLE = 19 and above) --
+      var_chunks_<branch>: a counted element whose cell has more than 64 live candidates (predecessor end, ancestor): more than one chunk
+      of a wavefront in both passes; var_same_<branch>: a counted element whose runner-up shares the winner's predecessor end and differs
+      in the ancestor (pass 1 must exclude the winner by both); var_shared_end_<branch>: an element of the path, counted or not, some two
+      live candidates of whose cell share a predecessor end"""
+    conds = set()
+    on = {(b, s): mk for b, s, rule, mk, mf in T.items if rule < 2}
+    tags = {0: "d0", 1: "d1", R - 2: "dR-2", R - 1: "dR-1"}
+    for b, e, s, _ in T.path:
+        if s not in chain_states:
+            continue
+        fl = [on[(q, s)] < eps for q in range(b, e + 1)]
+        slot = chain_states.index(s)
+        for i, f in enumerate(fl):
+            q, d = b + i, (e - b - i) % R
+            near = (i > 0 and fl[i - 1]) or (i + 1 < len(fl) and fl[i + 1])
+            if e - b + 1 > 2 * R:
+                for tag in ([tags[d]] if d in tags else []) + (["next0"] if e - q == R else []):
+                    if f:
+                        conds.add("flag_" + tag)
+                    elif near:
+                        conds.add("noflag_" + tag)
+            if f:
+                conds.add("slot%d" % slot)
+                # (trellis back-trace: the cells are counted from the loads of the walk; dense back-trace, dense.h:1434-1440: counted in a
+                # loop of its own that goes up from the entry cell of the run -- or base 1 -- 64 cells at a time, lane = cell - entry mod 64)
+                lane = (i % 64) if dense else (d % 128) // 2
+                if lane in (0, 63):
+                    conds.add("lane%d" % lane)
+                if dense and (e - b + 1) % 64 != 0 and i >= (e - b + 1) // 64 * 64:
+                    conds.add("flag_tail_chunk")  # (the last chunk of the count loop, some of whose lanes lie above the top of the run)
+        if b > 1:
+            d = (e - b) % R
+            conds.add("entry_flag" if fl[0] else "entry_noflag")
+            if d in (0, R - 1):
+                conds.add(("entry_flag_" if fl[0] else "entry_noflag_") + tags[d])
+        else:
+            conds.add("run_to_base1")
+            if fl[0]:
+                conds.add("flag_base1")
+        if e == T.n - 1 and fl[-1]:
+            conds.add("flag_last_base")
+    f = T.flags(eps)
+    for c, s in enumerate(chain_states):
+        if (f[1:, s] == 1).any():
+            conds.add("cells_slot%d" % c)
+    for b, s, rule, mk, mf in T.items:
+        if rule == 2 and 0 < mk < eps:
+            conds.add("var%d" % s)
+        if rule == 2 and mk == 0:
+            conds.add("var_tie")
+        if rule == 2 and 0 < mk < eps and kinds is not None:
+            # (the branch of the back-trace that takes the arg-max again: the UTR site list, or the candidate records of kCand)
+            br = "utr" if kinds[s] >= K_UTR5SINGLE else "rec"
+            if T.cands[(b, s)][0] > 64:
+                conds.add("var_chunks_" + br)
+            if T.cands[(b, s)][1]:
+                conds.add("var_same_" + br)
+        if rule == 2 and kinds is not None and T.cands[(b, s)][2]:
+            conds.add("var_shared_end_" + ("utr" if kinds[s] >= K_UTR5SINGLE else "rec"))
+    return conds
+
+
+# records the on-path assertions rest on: with TIES_EPS between 1 % and 50 % of the chain cells of the twin's path are flagged
+TIES_ON_PATH = {0: ("rand60k", "withN", "multigc_levels", "HS04636", "softmask_all", "multigc_two", "gt_cag", "orf12k", "multi_far", "gcsteps7_0", "gcsteps7_1"),
+                1: ("HS04636", "withN", "taa_after_gene", "aataaa_after_gene", "gene_N_runs", "twoclass_gene", "cut_11_1")}
+# prefixes found by a search over the twin's list (a chain run whose top is the end of the piece: the length of the prefix sets the
+# in-round distance of its cells): (golden record, length) -> the shape it is there for at TIES_EPS (ties_conditions)
+TIES_FOUND = {"human": (("HS04636", 2745), ("HS04636", 8951), ("withN", 8125), ("withN", 10173)),   # entry_flag_d0, entry_flag_dR-1, noflag_next0, flag_next0
+              "caenorhabditis": (("HS04636", 6904), ("HS04636", 8951), ("multigc_levels", 13652), ("rand60k", 7301)),  # the same four
+              "human_utr": (("HS04636", 1564), ("HS04636", 9113)),                                # entry_flag_d0, entry_flag_dR-1
+              "fly_utr": (("HS04636", 8850), ("HS04636", 9105), ("HS04636", 9367)), "human_atleastone": (("HS04636", 6904), ("HS04636", 7159)),
+              "maize": (("HS04636", 1164), ("HS04636", 1419))}
+# the same search for runs whose entry cell is NOT flagged at TIES_EPS (nearly every entry cell is): an edge case that ends in an intergenic
+# run with such an entry, a tail of random DNA behind it, cut to the length that puts the entry at in-round distance 0 / R - 1:
+# (edge case, seed of the tail, lengths)
+TIES_TAILS = {"human": ("orf12k", 4, (15136, 15137)), "caenorhabditis": ("orf12k", 4, (13007,)), "human_utr": ("cag_many", 4, (13520, 13775)),
+              "fly_utr": ("cag_many", 5, (13868, 14123)), "human_atleastone": ("orf12k", 4, (13089, 13344)), "maize": ("orf12k", 4, (13007, 13262))}
+
+
+# windows of 20 kb of the real DNA the soaks draw from (tests/soak_cli.py: real_dna; window w = bases 20 000 w .. 20 000 (w + 1)), found by
+# the same search: paths with a flagged cell in chain slot 3 (the geometric intron state of frame 2) and with counted elements of the
+# kinds the edge cases do not count
+# (negative: window -w in upper case -- a third of this DNA is soft-masked, and the masked bases are hints against exons)
+TIES_REAL_WINDOWS = {"maize": (7, 10, 31), "fly_utr": (1, 3, 4, 11, 28, 29, 38, -3, -4), "human_atleastone": (1, 3), "human_utr": (1, 3, 4, -1, -4)}
+_real_dna = None
+
+
+def ties_real_windows(cfg):
+    global _real_dna
+    if cfg not in TIES_REAL_WINDOWS:
+        return []
+    if _real_dna is None:
+        import soak_cli
+        _real_dna = soak_cli.real_dna()[1]
+    win = lambda w: _real_dna[abs(w) * 20000:(abs(w) + 1) * 20000]
+    return [("real[%d]%s" % (abs(w), " upper" if w < 0 else ""), win(w).upper() if w < 0 else win(w)) for w in TIES_REAL_WINDOWS[cfg]]
+
+
+def ties_tail_records(cfg):
+    base, seed, lens = TIES_TAILS[cfg]
+    R = emu_trellis_windows()["BT_ROUND_DENSE" if ties_family(cfg) else "BT_ROUND"]
+    tr = dict(trellis_edge_cases())
+    head = tr[base][:-1000] if base == "orf12k" else tr[base][:-2000]  # (the edge case without its own tail)
+    seq = head + random_dna((2200 if base == "orf12k" else 2000) + 3 * R, seed)
+    recs = [("%s_tail%d[:%d]" % (base, seed, n), seq[:n]) for n in lens]
+    if cfg == "caenorhabditis":  # (its second length came from another tail)
+        recs.append(("orf12k_tail9[:15054]", (head + random_dna(2200 + 3 * R, 9))[:15054]))
+    return recs
+
+
+def ties_n_jump_record():
+    """5 kb of the golden record withN on either side of a run of 3600 N, which the trellis jumps over (a run of 3000 it does not): the
+    twin's path is one intergenic run through it"""
+    w = dict(golden_inputs())["withN"]
+    return ("N_jump", w[15000:20000] + "N" * 3600 + w[23000:28000])
+
+
+def ties_records(cfg):
+    """[(name, sequence)] of the near-tie tests of one configuration: the golden records, the edge cases of the family's kernels, two
+    records whose GC content steps, pieces of a few bases, one intergenic run (prefixes of softmask_all) and runs of N of the lengths
+    around one, two and three rounds of the back-trace (tests/test_gpu_backtrace.py has every length 1..300 and 256 k + d up to 7 936
+    because it does not know the round; here R is exported and the lengths are the edges of the first three rounds), and the prefixes
+    and tails found by search (TIES_FOUND, TIES_TAILS)"""
+    fam = ties_family(cfg)
+    by = dict(golden_inputs())
+    R = emu_trellis_windows()["BT_ROUND_DENSE" if fam else "BT_ROUND"]
+    if fam:
+        recs = [(k, by[k]) for k in ("HS04636", "withN", "short7", "short100", "revcomp", "rand20k_b", "HS08198")]
+        recs += dense_edge_cases()
+    else:
+        recs = [(k, by[k]) for k in ("rand60k", "withN", "multigc_levels", "HS04636", "softmask_all", "multigc_two", "short7", "short100")]
+        recs += [(k, by[k]) for k in ("revcomp", "rand20k_b", "HS08198")]
+        recs += trellis_edge_cases() + gc_step_records(2, 7)
+        recs.append(("cag_dense", "ACGT" * 500 + "CAG" * 2500 + "ACGT" * 500))  # (dense_edge_cases: cells with more than 64 live candidates)
+        recs.append(ties_n_jump_record())
+    lens = sorted({1, 2, 3, 4} | {k * R + d for k in (1, 2, 3) for d in (-1, 0, 1, 2)})
+    recs += [("softmask_all[:%d]" % n, by["softmask_all"][:n]) for n in lens if n <= len(by["softmask_all"])]
+    recs += [("N*%d" % n, "N" * n) for n in lens if n <= 2 * R + 2]
+    recs += [("%s[:%d]" % (k, n), by[k][:n]) for k, n in TIES_FOUND.get(cfg, ())]
+    recs += ties_tail_records(cfg) + ties_real_windows(cfg)
+    assert len(set(n for n, _ in recs)) == len(recs)
+    return recs
+
+
+TIES_CORE = {"flag_d0", "flag_d1", "flag_dR-2", "flag_dR-1", "noflag_d0", "noflag_d1", "noflag_dR-2", "noflag_dR-1", "lane0", "lane63",
+             "run_to_base1", "flag_last_base", "entry_flag", "flag_next0", "noflag_next0", "entry_flag_d0", "entry_flag_dR-1", "entry_noflag",
+             "entry_noflag_d0", "entry_noflag_dR-1"}
+_DENSE_VAR = {"flag_tail_chunk", "var_tie", "var_chunks_rec", "var_same_rec", "var_chunks_utr", "var_same_utr"}
+# what the records of a configuration show at TIES_EPS on top of TIES_CORE (ties_conditions; asserted from the twin's output).  Not there:
+# a flagged cell at base 1 under the model with two intergenic states (its first intergenic state has one way in); UTR branches under the
+# models without UTR states; under the 47-state models no two live candidates of a variable-length cell share a predecessor end (one
+# feasible ancestor per end: lessD has one ancestor, the reading frame picks the one of an exon), so var_same_rec cannot exist there --
+# the tests assert that var_shared_end_rec is absent -- and no DNA with an exactly tied element was found (var_tie; DESIGN.md 6 lists the
+# searches): tests/test_emu_ties.py reaches that tie through the model (BumpedTables)
+TIES_SHAPES = {
+    "human": {"flag_base1", "var_chunks_rec"}, "caenorhabditis": {"flag_base1", "var_chunks_rec"},
+    "human_utr": {"flag_base1"} | _DENSE_VAR, "fly_utr": {"flag_base1"} | _DENSE_VAR,
+    "human_atleastone": {"flag_tail_chunk", "var_same_rec"}, "maize": {"flag_base1", "flag_tail_chunk", "var_chunks_rec"},
+}
+TIES_ONE_ANCESTOR_PER_END = ("human", "caenorhabditis", "maize")
+# What cannot be there.  Chain slot 0 under the model with two intergenic states: its first intergenic state has one way in, so its cells
+# have no runner-up and no flag.  Reverse single (AUGX_K_RSINGLE, 5) and reverse terminal (AUGX_K_RTERMINAL, 8) exons under the 47-state
+# models: one predecessor end, the reading frame's, and one ancestor -- one candidate, no runner-up (under the UTR models and under two
+# intergenic states they have more ancestors and ARE counted).  What is merely not there: the internal UTR exons of human --UTR=on (kinds
+# 23, 29, 35, 41: a UTR with two introns) -- none of the 50 windows of the real DNA, raw or in upper case, has one on its path under human;
+# fly --UTR=on counts 23, 35 and 41
+TIES_NO_SLOT = {"human_atleastone": {0}}
+TIES_KINDS_UNCOUNTED = {"human": {5, 8}, "caenorhabditis": {5, 8}, "maize": {5, 8}, "human_utr": {23, 29, 35, 41}, "fly_utr": set(), "human_atleastone": set()}
+
+
+def emu_seg_stops(lib=None):
+    """[(index in the piece, first tile, end tile, seg_stop, seg_stop2)] of the segments of the emulator's last decode by the trellis kernels
+    (tiles of 64 bases; the stops as Batch.plan gives them on the device)"""
+    out = np.zeros((64, 5), dtype=np.int32)
+    n = _emu_of(lib).emu_seg_stops(out.ctypes.data_as(ctypes.c_void_p), 64)
+    rows, k, prev = [], 0, None
+    for piece, t0, t1, stop, stop2 in out[:n].tolist():
+        k = k + 1 if piece == prev else 0
+        prev = piece
+        rows.append((k, t0, t1, stop, stop2))
+    return rows
+
+
+def ties_assert_rewritten_tiles(T, eps, segs, nocheck):
+    """the twin T of ONE piece decoded in segments has flagged chain cells in the tiles that a fix-up rewrote, in those a continuation
+    rewrote and -- nocheck: an unreachable check length -- in those left to the last pass.  segs: [(index in the piece, first tile, end
+    tile, seg_stop, seg_stop2)].  With an unreachable check length all four fix-ups give up; three are continued by the rounds of pass 3
+    and the fourth, the last segment's, is left to the last pass (tests/test_emu_trellis.py shows that from the emulator's counters; the
+    plan records where either stopped in the same field)"""
+    f = (T.flags(eps) == 1).any(axis=1)
+    fixed = continued = last = 0
+    for k, t0, t1, stop, stop2 in segs:
+        if k == 0:
+            continue
+        end = stop if stop >= t0 - 1 else -2 - stop  # (the last tile the fix-up rewrote, converged or not)
+        fixed += int(f[64 * t0:64 * (end + 1)].sum())
+        if stop <= -2 and stop2 >= 0:
+            continued += int(f[64 * (end + 1):64 * (stop2 + 1)].sum())
+            if nocheck and k == len(segs) - 1:
+                last += int(f[64 * (end + 1):64 * (stop2 + 1)].sum())
+    assert sum(1 for k, _, _, stop, _ in segs if k > 0 and stop <= -2) == (len(segs) - 1 if nocheck else 1), segs
+    assert fixed > 0 and continued > 0 and (last > 0 or not nocheck), (fixed, continued, last)
