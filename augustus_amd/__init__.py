@@ -62,6 +62,8 @@ def lib():
         L.augx_model_tables.argtypes = [ctypes.c_void_p]
         L.augx_model_option.restype = ctypes.c_char_p
         L.augx_model_option.argtypes = [ctypes.c_void_p, ctypes.c_char_p]
+        L.augx_model_layout.restype = ctypes.c_int
+        L.augx_model_layout.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32)]
         L.augx_model_destroy.argtypes = [ctypes.c_void_p]
         L.augx_device_count.restype = ctypes.c_int
         L.augx_partition_lpt.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
@@ -137,6 +139,13 @@ class Model:
     def option(self, name):
         v = lib().augx_model_option(self._h, name.encode())
         return None if v is None else v.decode()
+
+    def layout(self):
+        """(kernel family: "trellis" / "dense", block size, whether the initial exon candidates are in the late class of the dense kernels)
+        as ``augx_model_layout`` gives them, no device needed; AugxError(AUGX_E_UNSUPPORTED) with the reason for a model the decoder refuses"""
+        out = (ctypes.c_int32 * 3)()
+        _check(lib().augx_model_layout(self.tables_ptr, out))
+        return ("dense" if out[0] else "trellis", int(out[1]), bool(out[2]))
 
     def close(self):
         if self._h:

@@ -1293,6 +1293,17 @@ int augx_plan_segments(const augx_tables *t, const int64_t *lens, int n, int slo
     } catch (const std::exception &e) { setLastError(std::string("augx_plan_segments: ") + e.what()); return AUGX_E_ARG; }
 }
 
+int augx_model_layout(const augx_tables *t, int32_t *out) {
+    if (!t || !out) { setLastError("augx_model_layout: NULL argument"); return AUGX_E_ARG; }
+    try {
+        DevTables D;
+        const int blk = chooseBlockSize(*t);
+        fillDevTablesScalars(*t, D);
+        out[0] = D.dense; out[1] = blk; out[2] = D.lateInitial;
+        return AUGX_OK;
+    } catch (const std::exception &e) { setLastError(std::string("augx_model_layout: ") + e.what()); return AUGX_E_UNSUPPORTED; }
+}
+
 int augx_batch_plan(augx_decoder *d, augx_batch *b, int32_t *segs, int cap_segs, int *n_segs, int32_t *run_seg0, int cap_runs, int *n_runs,
                     int *check_tiles, int64_t *est, int32_t *seg_stop, int32_t *seg_stop2) {
     if (!d || !b) { setLastError("augx_batch_plan: NULL argument"); return AUGX_E_ARG; }

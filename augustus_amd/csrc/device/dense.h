@@ -804,7 +804,7 @@ struct DenseLds {
     unsigned long long csum[2][8][SPX]; // ... (forward) sum of exp(candidate - largest), fixed point
     double tr[SPX][AUGX_MAX_ANC];    // ln t(ancestor ai -> s) of the piece's first class (MODE 1: times the heat, as sg below)
     uint8_t anc[SPX][AUGX_MAX_ANC], nanc[SPX];
-    uint8_t cellKind[SPX];           // 1: candidates from the records of kCand, 2: reverse terminal exon, 3: UTR exon, 0: none
+    uint8_t cellKind[SPX];           // 1: candidates from the records of kCand, 2: those of the late class (dp.h: isLateKind), 3: UTR exon, 0: none
     double sg[2][8][NSIG];           // signal records of the block ([parity]; the next block's are staged meanwhile)
     uint64_t bOff[2];
     uint32_t bCnt[2][2];
@@ -882,7 +882,7 @@ AUGX_KFN void densePiece(const DevTables &T, const BatchView &B, DenseLds &L, in
         for (int i = t; i < 8 * SPX; i += NT) { (*lp(&L.cmax[0][i / SPX][i % SPX])) = AUGX_NINF; (*lp(&L.csum[0][i / SPX][i % SPX])) = 0ull; }
         if (t < SPX) {
             const int k = t < S && T.reachable[t] ? T.kind[t] : -1;
-            (*lp(&L.cellKind[t])) = k < 0 ? 0 : k == AUGX_K_RTERMINAL ? 2 : isItemKind(k) ? 1 : isUtrExonKind(k) ? 3 : 0;
+            (*lp(&L.cellKind[t])) = k < 0 ? 0 : isLateKind(T, k) ? 2 : isItemKind(k) ? 1 : isUtrExonKind(k) ? 3 : 0;
             (*lp(&L.nanc[t])) = (uint8_t)(t < S ? T.n_anc[t] : 0);
             for (int ai = 0; ai < AUGX_MAX_ANC; ai++) {
                 const int a = (t < S && ai < T.n_anc[t]) ? T.anc[t][ai] : 0;
@@ -1095,7 +1095,7 @@ AUGX_KFN void densePiece(const DevTables &T, const BatchView &B, DenseLds &L, in
         for (int ai = 0; ai < T.n_anc[s2]; ai++) {
             const int a = T.anc[s2][ai], ka = T.kind[a];
             const bool live = isChainKind(ka) && !isEarlyChainKind(ka);
-            if (!live && !((isItemKind(ka) && ka != AUGX_K_RTERMINAL) || isUtrExonKind(ka))) lateAcc = false;
+            if (!live && !((isItemKind(ka) && !isLateKind(T, ka)) || isUtrExonKind(ka))) lateAcc = false;
         }
     }
 #ifdef AUGX_EMU
@@ -1114,12 +1114,18 @@ AUGX_KFN void densePiece(const DevTables &T, const BatchView &B, DenseLds &L, in
             dj = (int)(I.kp >> (KEY_BITS + 7)); s2 = (int)((I.kp >> KEY_BITS) & 127);
             if (!(I.te > AUGX_NINF)) return AUGX_NINF;
             const int eop = (int)(I.kp & KEY_MASK) - KEY_BIAS;
-#ifdef AUGX_EMU // (stage 2 relies on it: a predecessor inside the block is a fixed-lag state, made in stage 1)
-            if (eop >= jb && T.kind[s2] != AUGX_K_RTERMINAL && !isFixedKind(T.kind[I.src & 127u]) && getenv("AUGX_EMU_CHECK_LAG"))
+#ifdef AUGX_EMU // (stage 2 relies on it: a predecessor inside the block is a fixed-lag state, made in stage 1; stage 5: one made in stages 1-4)
+            if (eop >= jb && !isLateKind(T, T.kind[s2]) && !isFixedKind(T.kind[I.src & 127u]) && getenv("AUGX_EMU_CHECK_LAG"))
                 fprintf(stderr, "emu: in-block predecessor that is not a fixed-lag state: state %d kind %d j %d eop %d jb %d src %d\n", s2, T.kind[s2], jb + dj, eop, jb, (int)(I.src & 127u));
+            if (eop >= jb && isLateKind(T, T.kind[s2]) && isLateKind(T, T.kind[I.src & 127u]) && getenv("AUGX_EMU_CHECK_LAG"))
+                fprintf(stderr, "emu: in-block predecessor of the late class that is of the late class itself: state %d kind %d j %d eop %d jb %d src %d\n", s2, T.kind[s2], jb + dj, eop, jb, (int)(I.src & 127u));
 #endif
             EDCALLER(0);
             const double pv = denseAt<FWD>(L, M, S, eop, (int)(I.src & 127u), jb, BLK);
+#ifdef AUGX_EMU // (AUGX_EMU_LATE_LOG=1: the live candidates of the late class that start from a cell of their own block, one line each)
+            if (!FWD && eop >= jb && pv > AUGX_NINF && isLateKind(T, T.kind[s2]) && getenv("AUGX_EMU_LATE_LOG"))
+                fprintf(stderr, "emu: late in-block: state %d kind %d j %d eop %d jb %d src %d\n", s2, T.kind[s2], jb + dj, eop, jb, (int)(I.src & 127u));
+#endif
             return pv + H(I.te);
         };
         auto itemPass = [&](uint32_t lo2, uint32_t hi2, bool sumPass) __attribute__((always_inline)) {
@@ -1296,7 +1302,7 @@ AUGX_KFN void densePiece(const DevTables &T, const BatchView &B, DenseLds &L, in
         if (nUv > 0) utrPass(false, -1);
         BLOCK_SYNC();
         DPROF(2);
-        // ---- 2: the records of kCand but RTERMINAL (their predecessors: earlier blocks, or fixed-lag states of this one); the early chain
+        // ---- 2: the records of kCand but those of the late class (their predecessors: earlier blocks, or fixed-lag states of this one); the early chain
         //         states (geometric introns: fed by the fixed-lag states of the base before and by themselves)
         itemPass(0, cntNonRT, false);
         FOR_THREADS(t) { if (t >= WAVE && t - WAVE < nEarly * BLK) chainOthers((t - WAVE) / BLK, (t - WAVE) % BLK, jb, par, false); }
@@ -1349,7 +1355,8 @@ AUGX_KFN void densePiece(const DevTables &T, const BatchView &B, DenseLds &L, in
         FOR_THREADS(t) { if (t >= nEarly && t < nCh) { if (TX(cFast)) chainRunSelf(t, TX(cS2), TX(cSelf), TX(cSgi), jb, par); else chainRun(t, jb, par); } }
         BLOCK_SYNC();
         DPROF(7);
-        // ---- 5: reverse terminal exons (they may start from a cell of their own block)
+        // ---- 5: the late class (dp.h: isLateKind): reverse terminal exons, and the initial exons of a model whose translation-initiation
+        //         window is shorter than the block.  They may start from a chain cell of their own block; nothing of the block reads theirs
         itemPass(cntNonRT, cntAll, false);
         BLOCK_SYNC();
         if (FWD) { itemPass(cntNonRT, cntAll, true); BLOCK_SYNC(); }

@@ -161,9 +161,15 @@ struct DevTables {
     TabPtr ln_trans, ig_emi, ig_short, in_emi, ex_emi, ex_init, ex_et, ex_pls, tis_motif, ass_motif,
         tis_bin_bounds, tis_bin_ln, ass_pat, dss_pat, len_intron, len_single, len_initial, len_internal,
         len_terminal;
-    double heat;               // augx_tables::heat: power of transition x emission in the forward summands (1.0: cold).  Last, so that
-                               // no field the Viterbi kernels read moves
+    double heat;               // augx_tables::heat: power of transition x emission in the forward summands (1.0: cold).  After every field the Viterbi
+                               // kernels of earlier builds read, so that none of them moves; so is what follows
+    int lateInitial;           // (dense kernels) the INITIAL candidates may start from a cell of their own block: they join the late class
+                               // of RTERMINAL (isLateKind below; layout.h: lateInitialFor decides it from the windows and the block)
 };
+// the late class of the dense kernels: variable-length states whose candidates are evaluated after the late chain states of their
+// block (dense.h: densePiece, stage 5), because their single predecessor may be a chain cell of that very block.  One definition for the
+// record order of kCand (kernels.h: varMasks), the cells and the stage order of densePiece.  The trellis kernels know RTERMINAL alone
+AUGX_HD bool isLateKind(const DevTables &T, int kind) { return kind == AUGX_K_RTERMINAL || (T.lateInitial && kind == AUGX_K_INITIAL); }
 
 // a batch of pieces laid out in one slot space.  Piece p owns slots [off[p], off[p+1]); slot off[p] is the
 // "before the first base" slot, base q lives in slot off[p]+1+q; off[p] is a multiple of CHUNK.

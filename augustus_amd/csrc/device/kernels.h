@@ -1131,13 +1131,15 @@ AUGX_KFN void varEvalItem(const CandCtx &X, int s, int j, const VarDesc &D, int 
 }
 
 // masks of the variable-length states: all but RTERMINAL / RTERMINAL (whose candidate may read the igenic cell of
-// its own block and is therefore ordered after the chain states in the trellis)
+// its own block and is therefore ordered after the chain states in the trellis).  The dense kernels take the second mask for their
+// whole late class (dp.h: isLateKind), to which a model with a short translation-initiation window adds INITIAL
+template <bool DENSE = false>
 AUGX_HD void varMasks(const DevTables &T, uint64_t &maskVar, uint64_t &maskRT) {
     maskVar = 0; maskRT = 0;
     for (int s2 = 0; s2 < T.S; s2++) {
         if (!T.reachable[s2]) continue;
         const int kind = T.kind[s2];
-        if (kind == AUGX_K_RTERMINAL) maskRT |= 1ull << T.vbit[s2];
+        if (DENSE ? isLateKind(T, kind) : kind == AUGX_K_RTERMINAL) maskRT |= 1ull << T.vbit[s2];
         else if ((kind >= AUGX_K_SINGLE && kind <= AUGX_K_RTERMINAL) || kind == AUGX_K_LESSD || kind == AUGX_K_RLESSD) maskVar |= 1ull << T.vbit[s2];
     }
 }
@@ -1445,7 +1447,7 @@ AUGX_KFN void candWorkgroup(const DevTables &T, const BatchView &B, CandLds &L, 
     CandCtx X(T, B, L.vc, p);
     X.P.lcode = L.codes; X.P.lLo = cLo; X.P.lHi = cLo + NWAVES * WAVE + 2 * WAVE;
     uint64_t maskVar, maskRT;
-    varMasks(T, maskVar, maskRT);
+    varMasks<DENSE>(T, maskVar, maskRT);
     uint64_t maskLess = 0;
     for (int s2 = 0; s2 < X.S; s2++)
         if (T.kind[s2] == AUGX_K_LESSD || T.kind[s2] == AUGX_K_RLESSD) maskLess |= 1ull << T.vbit[s2];

@@ -324,6 +324,17 @@ inline void checkForwardSum(const augx_tables &t) {
     if (forwardCellCandidates(t) > FWD_SUM_TERMS) throw std::runtime_error("augx: exon or intron lengths too large for the fixed-point sums of the forward pass");
 }
 
+// Shortest distance from the end of a single / initial exon state back to the end of its predecessor, as the windows give it
+// (reference src/exonmodel.cc:1042-1061).  The state begins with the translation-initiation window (W bases) and the start codon and
+// ends dss_start bases before the donor site, so the shortest exon leaves it W + minexonlength - dss_start bases -- the reference
+// clamps the state to one base where this is less ("ensure that base>endOfPred", :1052-1053), so a value below 1 stands for 1.  W
+// alone bounds the same two kinds from the window side (bpl = 3 + W is the only begin part that holds it, dp.h: exGeom): whichever
+// term is smaller, the candidates it speaks of are those of INITIAL; SINGLE is longer than min_coding_len whatever the windows
+inline int shortestInitialReach(const augx_tables &t) {
+    const int slack = t.W + t.min_exon_len - t.Ds;
+    return t.W < slack ? t.W : slack;
+}
+
 inline void checkModelSupported(const augx_tables &t, int BLK) {
     checkForwardSum(t);
     if (t.S > SP) throw std::runtime_error("augx: model has more than 48 states: not for the wavefront layout of the trellis kernel (models with UTR states or two intergenic states go to the dense kernels, modelIsDense below)");
@@ -384,9 +395,10 @@ inline void checkModelSupported(const augx_tables &t, int BLK) {
                 if (kind == AUGX_K_IGENIC && isChain(ak) && t.anc[s][a] != s) throw std::runtime_error("augx: intergenic state fed by an intron state");
             }
         }
-        // single / initial exons reach back to an igenic cell at least this far (reference src/exonmodel.cc:1042-1054)
-        int slack = t.W + t.min_exon_len - t.Ds;
-        if (t.W < slack) slack = t.W;
+        // single / initial exons reach back to an igenic cell at least this far (reference src/exonmodel.cc:1042-1054).  The dense
+        // kernels take a model whose reach is shorter than any block (chooseDenseBlock: the late class); this kernel's far wavefront
+        // would finish such cells one or two blocks later, and the donor-side states that read them are nearer than that
+        const int slack = shortestInitialReach(t);
         if (slack < BLK) throw std::runtime_error("augx: trans_init_window too short for the block size of the trellis kernel");
     }
     {   // the fixed-lag states are laid out in rounds of 8: near / late states (lag < 3 blocks) first, then the far ones
@@ -412,8 +424,9 @@ inline bool modelIsDense(const augx_tables &t) {
     if (t.utr != 0 || nIg > 1) return true;
     // a 47-state model whose windows the wavefront layout of the trellis kernel was not built for (an equalD state that looks back 57-63
     // bases; splice-site windows of more than 63 bases; a translation-initiation window shorter than the smallest block) goes to the
-    // state-graph driven dense kernels as well, where they take it (round 6: Vitrella_brassicaformis, maize, Micromonas_pusilla,
-    // Rhopilema_esculentum -- slower there, but the reference's result instead of a refusal)
+    // state-graph driven dense kernels as well, where they take it -- slower there, but the reference's result instead of a refusal:
+    // Vitrella_brassicaformis and maize for their windows, and Micromonas_pusilla, Rhopilema_esculentum, galdieria and schistosoma, whose
+    // shortest initial exon state reaches back one base: there the INITIAL candidates join the late class (shortestInitialReach above, chooseDenseBlock below)
     try { checkModelSupported(t, 2); return false; } catch (std::exception &) {}
     for (int b = 4; b <= 8; b *= 2) { try { checkModelSupported(t, b); return false; } catch (std::exception &) {} }
     try { (void)chooseDenseBlock(t); return true; } catch (std::exception &) { return false; } // (neither: chooseBlockSize reports the trellis kernel's reason)
@@ -427,9 +440,7 @@ inline int chooseDenseBlock(const augx_tables &t) {
     const int dssWhole = t.Ds + 2 + t.De, assLag = t.As + 2 + t.Ae + t.U, dL = t.d - 2 - t.De - t.As - 2 - t.U;
     int lag = dssWhole < assLag ? dssWhole : assLag;
     if (dL < lag) lag = dL;
-    int slack = t.W + t.min_exon_len - t.Ds; // single / initial exons reach back to their predecessor at least this far
-    if (t.W < slack) slack = t.W;
-    if (slack < lag) lag = slack;
+    const int slack = shortestInitialReach(t);
     if (t.utr) {
         DevTables D;
         memset(&D, 0, sizeof D);
@@ -459,12 +470,38 @@ inline int chooseDenseBlock(const augx_tables &t) {
         }
     }
     if (nChain > 16 || nFix > 24 || nUv > 16) throw std::runtime_error("augx: state graph too large for the dense kernels");
-    int b = 8;
-    if (const char *e = getenv("AUGX_BLK")) b = atoi(e);
+    int b0 = 8;
+    if (const char *e = getenv("AUGX_BLK")) b0 = atoi(e);
+    // where the shortest initial exon state reaches back a block or more, it bounds the block like every other lag
+    int b = b0;
+    while (b > 1 && (b > lag || b > slack)) b /= 2;
+    if (b >= 2) return b;
+    // It reaches back less than the smallest block (translation-initiation windows of 0-3 bases): the block follows from the other
+    // lags, and the INITIAL candidates join the late class of densePiece (dp.h: isLateKind; lateInitialFor below), evaluated when the
+    // chain cells of their block exist.  What READS an INITIAL cell must then lie a block or more behind it, the analogue of the
+    // rule for RTERMINAL above: only fixed-lag states may read it.  (Their lag is the block at least whatever the model: the block was
+    // just chosen below every fixed lag.  So the loop below refuses exactly the readers that are chain or variable-length states.)
+    // Models with UTR states are left out: there the in-block predecessor of INITIAL would be a 5' UTR exon cell of stage 3, an order
+    // that holds but that no shipped species can test (galdieria --UTR=on is refused for its UTR windows before it gets here)
+    b = b0;
     while (b > 1 && b > lag) b /= 2;
-    if (b < 2) throw std::runtime_error("augx: signal windows too short for the dense kernels");
+    if (b < 2 || t.utr) throw std::runtime_error("augx: signal windows too short for the dense kernels");
+    // (SINGLE shares the begin part of INITIAL; its length distribution is empty below min_coding_len: model.cc)
+    if (t.W + t.min_coding_len < b) throw std::runtime_error("augx: min_coding_len too short for the block size of the dense kernels");
+    for (int s = 0; s < t.S; s++) {
+        if (!t.reachable[s]) continue;
+        const int k = t.state_kind[s];
+        const int fl = (k == AUGX_K_LONGASS || k == AUGX_K_RLONGASS) ? assLag : (k == AUGX_K_LONGDSS || k == AUGX_K_RLONGDSS) ? dssWhole
+                       : (k == AUGX_K_EQUALD || k == AUGX_K_REQUALD) ? dL : 0;
+        for (int a = 0; a < t.n_anc[s]; a++)
+            if (t.state_kind[t.anc[s][a]] == AUGX_K_INITIAL && fl < b)
+                throw std::runtime_error("augx: trans_init_window too short for the dense kernels: the initial exon state is read by a state nearer than one block");
+    }
     return b;
 }
+// whether the INITIAL candidates of this model are in the late class of the dense kernels at the block chooseDenseBlock gives it
+// (DevTables::lateInitial).  Off for every model whose shortest reach covers a block: nothing of their decode changes
+inline bool lateInitialFor(const augx_tables &t, int blk) { return shortestInitialReach(t) < blk; }
 
 // block size of the candidate / trellis kernels for this model: 8 where the species' windows allow it, else 4 or 2
 // (override for tests: AUGX_BLK=4).  Throws what checkModelSupported throws for the smallest size.
@@ -505,6 +542,8 @@ inline void fillDevTablesScalars(const augx_tables &t, DevTables &D) {
     D.tss_n = t.tss_n; D.tss_k = t.tss_k; D.tsstata_n = t.tsstata_n; D.tsstata_k = t.tsstata_k; D.tata_n = t.tata_n; D.tata_k = t.tata_k;
     D.tts_n = t.tts_n; D.tts_k = t.tts_k; D.ln_tts_rand = t.ln_tts_rand; D.ln2 = t.ln2;
     D.dense = modelIsDense(t);
+    D.lateInitial = 0;
+    if (D.dense) { try { D.lateInitial = lateInitialFor(t, chooseDenseBlock(t)); } catch (std::exception &) {} } // (a refused model: the decoder reports it)
     D.heat = t.heat;
     {   // end-gate bits of the variable-length states: the state index while it fits a 64-bit mask, else a compact numbering
         int nb = 0;

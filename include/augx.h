@@ -324,6 +324,12 @@ int augx_plan_segments(const augx_tables *t, const int64_t *lens, int n, int slo
                        int32_t *run_seg0 /* [cap_runs + 1] */, int cap_runs, int *n_runs, int *check_tiles, int64_t *est /* [2] */);
 int augx_batch_plan(augx_decoder *d, augx_batch *b, int32_t *segs, int cap_segs, int *n_segs, int32_t *run_seg0, int cap_runs, int *n_runs,
                     int *check_tiles, int64_t *est, int32_t *seg_stop /* [cap_segs] */, int32_t *seg_stop2 /* [cap_segs] */);
+/* How a model is laid out on the device, without a device: out[0] kernel family (0 trellis, 1 dense), out[1] block size (8, 4 or 2;
+ * AUGX_BLK in the environment applies), out[2] 1 where the candidates of the initial exon states are in the late class of the dense
+ * kernels -- models whose trans_init_window leaves the shortest initial exon state less than one block (schistosoma, galdieria,
+ * Micromonas_pusilla, Rhopilema_esculentum), 0 for every other model.  AUGX_E_UNSUPPORTED with the reason in augx_last_error where
+ * augx_decoder_create would refuse the model for its state graph or windows */
+int augx_model_layout(const augx_tables *t, int32_t *out /* [3] */);
 /* test hook: copy the dense ln V[j][s] matrix (len*S doubles, -inf = absent) of piece i to host; only
  * valid on a decoder created with AUGX_DEBUG_CELLS=1 in the environment */
 int augx_batch_cells(augx_decoder *d, augx_batch *b, int piece, double *out);
