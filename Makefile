@@ -78,7 +78,7 @@ oracle: oracle/libghmm_twin.so
 oracle/libghmm_twin.so: oracle/ghmm_twin.cc include/augx.h
 	$(CXX) $(CXXFLAGS) -shared -o $@ oracle/ghmm_twin.cc
 
-emu: build/libaugx_emu.so build/libaugx_emu_pl1.so build/libaugx_emu_slowq.so build/libaugx_emu_smallwin.so
+emu: build/libaugx_emu.so build/libaugx_emu_pl1.so build/libaugx_emu_slowq.so build/libaugx_emu_smallwin.so build/libaugx_emu_dense_seg.so
 build/libaugx_emu.so: tests/emu/emu.cc $(DEVHDR) include/augx.h
 	@mkdir -p build
 	$(CXX) $(CXXFLAGS) -shared -o $@ tests/emu/emu.cc
@@ -101,6 +101,11 @@ SMALLWIN = -DAUGX_ITEM_CAP=1024 -DAUGX_LIST_WIN=128 -DAUGX_VIG_WIN=128 -DAUGX_UD
 build/libaugx_emu_smallwin.so: tests/emu/emu.cc $(DEVHDR) include/augx.h
 	@mkdir -p build
 	$(CXX) $(CXXFLAGS) $(SMALLWIN) -shared -o $@ tests/emu/emu.cc
+
+# the emulator plus an entry that decodes the pieces of a dense model in segments (dense.h: denseTiles; tests/test_emu_dense_seg.py)
+build/libaugx_emu_dense_seg.so: tests/emu/emu_dense_seg.cc tests/emu/emu.cc $(DEVHDR) include/augx.h
+	@mkdir -p build
+	$(CXX) $(CXXFLAGS) -shared -o $@ tests/emu/emu_dense_seg.cc
 
 ref:
 	$(MAKE) -C oracle -j8

@@ -62,6 +62,8 @@ def lib():
         L.augx_model_tables.argtypes = [ctypes.c_void_p]
         L.augx_model_option.restype = ctypes.c_char_p
         L.augx_model_option.argtypes = [ctypes.c_void_p, ctypes.c_char_p]
+        L.augx_model_segmentable.restype = ctypes.c_int
+        L.augx_model_segmentable.argtypes = [ctypes.c_void_p]
         L.augx_model_layout.restype = ctypes.c_int
         L.augx_model_layout.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32)]
         L.augx_model_destroy.argtypes = [ctypes.c_void_p]
@@ -146,6 +148,11 @@ class Model:
         out = (ctypes.c_int32 * 3)()
         _check(lib().augx_model_layout(self.tables_ptr, out))
         return ("dense" if out[0] else "trellis", int(out[1]), bool(out[2]))
+
+    def segmentable(self):
+        """``augx_model_segmentable``: can pieces of this model be cut into segments, by whichever kernel family decodes it?  (Never:
+        the models with two intergenic states, ``genemodel=atleastone`` / ``exactlyone``; the forward pass of any model)"""
+        return bool(lib().augx_model_segmentable(self.tables_ptr))
 
     def close(self):
         if self._h:

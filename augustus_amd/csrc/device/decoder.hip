@@ -454,6 +454,7 @@ void launchCand(int blk, bool multi, bool dense, unsigned grid, hipStream_t st, 
 void launchForward(int blk, unsigned grid, hipStream_t st, const DevTables *T, const BatchView *B) { AUGX_BY_BLK(launchForward_, grid, st, T, B); }
 void launchDense(int blk, int mode, bool ties, unsigned grid, hipStream_t st, const DevTables *T, const BatchView *B) { AUGX_BY_BLK(launchDense_, mode, ties, grid, st, T, B); }
 void launchUtrDesc(int blk, unsigned grid, hipStream_t st, const DevTables *T, const BatchView &W) { AUGX_BY_BLK(launchUtrDesc_, grid, st, T, W); }
+void launchDenseSeg(int blk, int pass, bool ties, unsigned grid, hipStream_t st, const DevTables *T, const BatchView *B) { AUGX_BY_BLK(launchDenseSeg_, pass, ties, grid, st, T, B); }
 #undef AUGX_BY_BLK
 }} // namespace
 
@@ -961,7 +962,7 @@ int augx_batch_create(augx_decoder *d, const augx_piece *pieces, int n, augx_bat
     }
     keep(V.pathRec, Z.pathCap * 3);
     // segments of the trellis: enough workgroups for every compute unit, none shorter than what a fix-up needs
-    b->plan = planSegments(L, d->model->m.t, d->nCU / d->share > 0 ? d->nCU / d->share : 1, d->dense ? -1 : 0); // (dense kernels: one workgroup per piece)
+    b->plan = planSegments(L, d->model->m.t, d->nCU / d->share > 0 ? d->nCU / d->share : 1, 0, pieces); // (dense kernels: cut only with fewer pieces than workgroup slots)
     SegDesc *dSegs = nullptr; int32_t *dSeg0 = nullptr, *dRun0 = nullptr;
     const int nSegs = (int)b->plan.segs.size(), nRuns = b->plan.nRuns();
     keep(dSegs, nSegs); keep(dSeg0, n + 1);
@@ -971,7 +972,7 @@ int augx_batch_create(augx_decoder *d, const augx_piece *pieces, int n, augx_bat
     if (const char *e = getenv("AUGX_SEG_CHECK_TILES")) V.segCheckTiles = atoi(e); // (tests of the give-up path: an unreachable check length)
     keep(V.segStop, nSegs); keep(V.segStatus, nSegs); keep(V.segD, nSegs); keep(V.brkPos, nSegs); keep(V.brkOff, nSegs);
     keep(V.segStop2, nSegs); keep(V.segD2, nSegs); keep(V.pieceCovered, n);
-    if (b->plan.cut()) {
+    if (b->plan.cut() && !d->dense) { // (the dense kernels compare in place, in the matrix)
         keep(V.ckRing, (int64_t)nSegs * 2 * WAVE * SP); keep(V.ckCol, Z.N / WAVE * SP);
         keep(V.tileMinEop, Z.N / WAVE); keep(V.tileCross, Z.N / WAVE);
     }
@@ -1174,11 +1175,21 @@ int augx_batch_decode(augx_decoder *d, augx_batch *b) {
                         "prep launches + candidate buffer + candidates counted %.3f s (hipMalloc so far: %.3f s for %.1f GB)\n", tf[1] - tf[0], tf[2] - tf[1], b->V.nPl, tf[3] - tf[2], tf[4] - tf[3],
                 d->mallocSeconds, d->mallocBytes / 1e9);
     }
-    if (b->plan.cut()) hipLaunchKernelGGL(kTileCross, dim3((unsigned)((V.N / WAVE + 255) / 256)), dim3(256), 0, st, V); // how far back the future reads (fix-ups)
+    if (b->plan.cut() && !d->dense) hipLaunchKernelGGL(kTileCross, dim3((unsigned)((V.N / WAVE + 255) / 256)), dim3(256), 0, st, V); // how far back the future reads (fix-ups)
     HIP_TRY(hipEventRecord(b->ev[1], st));
     auto runTrellis = [&]() -> int { // the trellis passes and the back-trace (run again when candidate terms were rebuilt, see below)
     if (d->dense) { // the dense kernels: one workgroup per piece, the matrix in HBM (dense.h)
-        launchDense(d->blk, 0, V.nearTie, (unsigned)n, st, d->dT, b->dV); // (near ties counted: the build whose chain runs flag them)
+        if (!b->plan.cut()) launchDense(d->blk, 0, V.nearTie, (unsigned)n, st, d->dT, b->dV); // (near ties counted: the build whose chain runs flag them)
+        else { // pieces in segments (dense.h: denseTiles): every segment at once, the fix-ups, the continuation of the ones that gave up
+            HIP_TRY(hipMemsetAsync(V.segStatus, 0, sizeof(int32_t) * V.nSegs, st));
+            HIP_TRY(hipMemsetAsync(V.segStop2, 0xFF, sizeof(int32_t) * V.nSegs, st));
+            HIP_TRY(hipMemsetAsync(V.pieceCovered, 0xFF, sizeof(int32_t) * n, st));
+            HIP_TRY(hipMemsetAsync(V.segStop, 0xFF, sizeof(int32_t) * V.nSegs, st)); // (-1: no fix-up, or one that rewrote nothing)
+            launchDenseSeg(d->blk, 1, V.nearTie, (unsigned)V.nSegs, st, d->dT, b->dV);
+            launchDenseSeg(d->blk, 2, V.nearTie, (unsigned)V.nSegs, st, d->dT, b->dV);
+            launchDenseSeg(d->blk, 3, V.nearTie, (unsigned)n, st, d->dT, b->dV);
+            hipLaunchKernelGGL(kSegFinalize, dim3((n + 63) / 64), dim3(64), 0, st, V);
+        }
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(b->ev[2], st));
         hipLaunchKernelGGL(kDenseBacktrace, dim3(n), dim3(64), 0, st, d->dT, V);
@@ -1239,7 +1250,7 @@ int augx_batch_decode(augx_decoder *d, augx_batch *b) {
         }
     }
     HIP_TRY(hipEventRecord(b->ev[3], st));
-    if (timingFirst && !d->dense) { // (developer aid: the plan of the trellis passes and what became of its fix-ups)
+    if (timingFirst && (!d->dense || b->plan.cut())) { // (developer aid: the plan of the trellis passes and what became of its fix-ups)
         const SegPlan &P = b->plan;
         int longestSeg = 0, longestRun = 0, gaveUp = 0;
         for (const SegDesc &sd : P.segs) if (sd.t1 - sd.t0 > longestSeg) longestSeg = sd.t1 - sd.t0;
@@ -1289,8 +1300,13 @@ int augx_plan_segments(const augx_tables *t, const int64_t *lens, int n, int slo
         for (int p = 0; p < n; p++) { pieces[p].seq = nullptr; pieces[p].len = lens[p]; pieces[p].init_kind = 0; pieces[p].term_kind = 0; }
         BatchLayout L;
         L.build(pieces.data(), n);
-        return planOut(planSegments(L, *t, slots, modelIsDense(*t) ? -1 : 0), segs, cap_segs, n_segs, run_seg0, cap_runs, n_runs, check_tiles, est);
+        return planOut(planSegments(L, *t, slots), segs, cap_segs, n_segs, run_seg0, cap_runs, n_runs, check_tiles, est);
     } catch (const std::exception &e) { setLastError(std::string("augx_plan_segments: ") + e.what()); return AUGX_E_ARG; }
+}
+
+int augx_model_segmentable(const augx_tables *t) {
+    if (!t) { setLastError("augx_model_segmentable: NULL argument"); return 0; }
+    try { return modelSegmentable(*t) ? 1 : 0; } catch (const std::exception &) { return 0; }
 }
 
 int augx_model_layout(const augx_tables *t, int32_t *out) {

@@ -820,14 +820,21 @@ struct DenseLds {
     const double *lenTab[9];
     int lenMax[9];
     const USite *siteTab[6];
+    // a fix-up of a segment (denseTiles, pass 2): the offset the current tile is compared with, the one its last synch cell gave,
+    // whether a cell of the tile differed, consecutive verified tiles, and the decision taken at the tile's end
+    double fxD, fxDn;
+    int fxBad, fxRun, fxStop;
 };
 static_assert(UDCAP >= 1, "AUGX_UDCAP: the staging loops copy min(count, UDCAP) descriptors; at least one");
 static_assert(sizeof(DenseLds) <= 160 * 1024, "AUGX_UDCAP: DenseLds must fit the LDS of a workgroup");
 
 // value of state a at base q for the block that begins at jb: from the ring while no base of the block has taken its column
-template <bool FWD> AUGX_KFN double denseAt(const DenseLds &L, const double *M, int S, int q, int a, int jb, int BLK) {
+// (jDead > 0: a segment run from a dead start at base jDead -- nothing before it is alive but the synch state of the base before, at
+//  value 0; those rows belong to another workgroup and are not read)
+template <bool FWD> AUGX_KFN double denseAt(const DenseLds &L, const double *M, int S, int q, int a, int jb, int BLK, int jDead = 0, int synch = 0) {
     if (q < 0) q = 0;
     EDC(ED_AT_63 + g_emuDenseCaller, jb + BLK - 1 - q == WAVE - 1); EDC(ED_AT_64 + g_emuDenseCaller, jb + BLK - 1 - q == WAVE);
+    if (jDead > 0 && q < jDead) return (q == jDead - 1 && a == synch) ? 0.0 : AUGX_NINF;
     if (jb + BLK - 1 - q < WAVE) return ldsLoadD(&L.ring[q & 63][a]);
     return ldCoherent(&M[(int64_t)q * S + a]);
 }
@@ -839,10 +846,46 @@ template <bool FWD> AUGX_KFN double denseAt(const DenseLds &L, const double *M, 
 #endif
 // One workgroup walks piece p block by block.  MODE 0: Viterbi (ln V into B.cells, back pointers of the chain / fixed-lag
 // states into B.bpD, score and final state of the piece); MODE 1: forward algorithm (ln F into B.fwd, ln P(sequence)).
-template <int BLK, int MODE, bool TIES = false> // TIES (MODE 0): the chain runs flag near ties (dp.h: AUGX_NEAR_TIE) -- a build of its own
-AUGX_KFN void densePiece(const DevTables &T, const BatchView &B, DenseLds &L, int p) {
+//
+// SEG > 0 (MODE 0 only; a build per pass: the three share little but the recurrence, and one body for all of them spills): the piece
+// may be cut into segments of whole tiles (dp.h: SegDesc; the passes are those of the trellis), and the body runs a range of tiles
+// in pass SEG.  `pass` 1: segment `segIdx` -- the first of a piece as the whole run does, stopping at the segment's
+// end; a later one from a dead start (denseAt), clearing only its own rows.  `pass` 2: the fix-up of segment `segIdx` >= 1: the ring
+// is loaded from the 64 rows before the segment, final in the frame of what lies before; every cell is made again, compared with
+// the stored one (new == old + D, D from the synch state) and stored; after segCheckTiles consecutive tiles that verified with one D
+// the fix-up records segStop / segD and ends; at SegDesc::tlim it gives up.  `pass` 3 (one workgroup per piece): the earliest
+// fix-up of the piece that gave up goes on from there to the end of the piece without comparing.  Only the run that makes the
+// last tile of the piece writes its score, final state and status -- in the frame of that run (kernels.h: segFinalizePiece).
+// The decisions of a fix-up are taken by one thread into LDS and read after a barrier: every barrier stays in uniform control flow.
+template <int BLK, int MODE, bool TIES, int SEG>
+AUGX_KFN void denseTiles(const DevTables &T, const BatchView &B, DenseLds &L, int p, int segIdx) {
     constexpr bool FWD = MODE == 1;
+    constexpr int pass = SEG;
+    static_assert(!(SEG && FWD), "the forward recurrence is not exact: it is never run in segments");
     const int n = B.len[p], S = T.S, c0 = B.cls[p];
+    int jA_ = 0, jE_ = n, segQ = segIdx, tlim = 0;
+    bool dead_ = false;
+    if (SEG) { // (uniform: the plan and what the passes before left)
+        const int s0 = B.pieceSeg0[p], K = B.pieceSeg0[p + 1] - s0;
+        if (K <= 1) { if (pass != 1) return; } // a piece that is not cut: pass 1 does all of it
+        else if (pass == 3) {
+            segQ = -1;
+            for (int q = s0 + 1; q < s0 + K && segQ < 0; q++) if (B.segStop[q] <= -2) segQ = q;
+            if (segQ < 0) return;
+            jA_ = (-2 - B.segStop[segQ] + 1) * WAVE;
+            if (jA_ >= n) return;
+        } else {
+            const SegDesc sd = B.segs[segIdx];
+            if (pass == 2 && sd.k == 0) return; // (the first segment of a piece has no fix-up)
+            jA_ = sd.t0 * WAVE;
+            if (pass == 1) { jE_ = sd.t1 * WAVE < n ? sd.t1 * WAVE : n; dead_ = sd.k > 0; }
+            else tlim = sd.tlim;
+        }
+    }
+    // first base and end of the range; dead: from a dead start; over: the rows hold an earlier run's cells, every cell is stored
+    // (an absent one as -inf); cmp: and compared first
+    const int jA = SEG ? jA_ : 0, jE = SEG ? jE_ : n, jDead = (SEG && dead_) ? jA_ : 0;
+    constexpr bool over = SEG >= 2, cmp = SEG == 2;
     const int64_t o = B.off[p];
     double *M = (FWD ? B.fwd : B.cells) + (o + 1) * S;
     uint8_t *BP = B.bpD ? B.bpD + (o + 1) * S : nullptr;
@@ -890,17 +933,25 @@ AUGX_KFN void densePiece(const DevTables &T, const BatchView &B, DenseLds &L, in
                 (*lp(&L.tr[t][ai])) = (t < S && ai < T.n_anc[t]) ? H(lnT(T, c0, a, t)) : AUGX_NINF;
             }
         }
-        for (int64_t i = t; i < (int64_t)n * S; i += NT) gp(M)[i] = AUGX_NINF; // (absent cells stay -inf)
-        if (!FWD && BP) for (int64_t i = t; i < (int64_t)n * S; i += NT) gp(BP)[i] = 0xFF;
+        if (!over) { // (the rows of this run only; a run that stores every cell clears nothing)
+            for (int64_t i = (int64_t)jA * S + t; i < (int64_t)jE * S; i += NT) gp(M)[i] = AUGX_NINF; // (absent cells stay -inf)
+            if (!FWD && BP) for (int64_t i = (int64_t)jA * S + t; i < (int64_t)jE * S; i += NT) gp(BP)[i] = 0xFF;
+        }
+        if (SEG && t == 0) { (*lp(&L.fxD)) = AUGX_NINF - AUGX_NINF; (*lp(&L.fxDn)) = AUGX_NINF - AUGX_NINF; (*lp(&L.fxBad)) = 0; (*lp(&L.fxRun)) = 0; (*lp(&L.fxStop)) = 0; } // (no offset yet: NaN equals nothing)
     }
+    if (SEG && (jA > 0 || jE < n)) anyNuc = true; // (the planner never cuts a piece without a nucleotide)
     for (int q = 0; q < n && !anyNuc; q++) anyNuc = B.code[o + 1 + q] < 4; // (uniform; the pieces that are all N are rare and short-circuited below)
     BLOCK_GLOBAL_SYNC();
-    FOR_THREADS(t) { // column 0 = initial probabilities (reference NAMGene::setStatesInitialProbs, src/namgene.cc:144-150)
-        if (t < S) {
-            const double v = initLn(T, initKind, t);
-            (*lp(&L.ring[0][t])) = v;
-            gp(M)[t] = v;
-        }
+    FOR_THREADS(t) {
+        if (jA == 0) { // column 0 = initial probabilities (reference NAMGene::setStatesInitialProbs, src/namgene.cc:144-150)
+            if (t < S) {
+                const double v = initLn(T, initKind, t);
+                (*lp(&L.ring[0][t])) = v;
+                gp(M)[t] = v;
+            }
+        } else if (!over) { if (t == 0) (*lp(&L.ring[(jA - 1) & 63][synch])) = 0.0; } // dead start: the synch state of the base before, nothing else
+        else // the 64 columns before the range, as the runs before left them
+            for (int i = t; i < WAVE * S; i += NT) { const int q = jA - WAVE + i / S; (*lp(&L.ring[q & 63][i % S])) = gp(M)[(int64_t)q * S + i % S]; }
     }
     BLOCK_GLOBAL_SYNC();
     // ---- the states by role (uniform)
@@ -931,7 +982,7 @@ AUGX_KFN void densePiece(const DevTables &T, const BatchView &B, DenseLds &L, in
         }
         return;
     }
-    const int nBlocks = (n + BLK - 1) / BLK;
+    const int bA = jA / BLK, nBlocks = (jE + BLK - 1) / BLK; // (blocks [bA, nBlocks) of the piece; bA is even: a range begins with a tile)
     const int64_t gb0 = o / BLK;
     // per-thread constants of the fixed-lag step (thread = (state, base of the block))
     // stage 1: the threads below A1T make the fixed-lag states and stage the next block; the wavefronts from UW0 on take the UTR units
@@ -985,18 +1036,32 @@ AUGX_KFN void densePiece(const DevTables &T, const BatchView &B, DenseLds &L, in
         }
     }
     constexpr int NTW = NT - WAVE;
-    FOR_THREADS(t) { // block 0: offsets, signal records, gates
-        if (t == NT - 1) { (*lp(&L.bOff[0])) = gp(gBlkOff)[gb0 * 2 + 1]; (*lp(&L.bCnt[0][0])) = gp(gBlkCnt)[gb0 * 2 + 1]; (*lp(&L.bCnt[0][1])) = gp(gBlkSplit)[gb0 * 3 + 2]; }
-        if (t >= NT - BLK * NSIG) { const int i = t - (NT - BLK * NSIG); (*lp(&L.sg[0][i / NSIG][i % NSIG])) = i / NSIG < n ? H(gp(gSig)[(int64_t)(i / NSIG) * NSIG + i % NSIG]) : AUGX_NINF; }
-        if (nUv > 0) { // the descriptors of block 0
-            const uint64_t uo = gp(gUdOff)[gb0];
-            const uint32_t uc = gp(gUdCnt)[gb0];
+    FOR_THREADS(t) { // the first block: offsets, signal records, gates
+        if (t == NT - 1) { (*lp(&L.bOff[0])) = gp(gBlkOff)[(gb0 + bA) * 2 + 1]; (*lp(&L.bCnt[0][0])) = gp(gBlkCnt)[(gb0 + bA) * 2 + 1]; (*lp(&L.bCnt[0][1])) = gp(gBlkSplit)[(gb0 + bA) * 3 + 2]; }
+        if (t >= NT - BLK * NSIG) { const int i = t - (NT - BLK * NSIG); (*lp(&L.sg[0][i / NSIG][i % NSIG])) = jA + i / NSIG < n ? H(gp(gSig)[(int64_t)(jA + i / NSIG) * NSIG + i % NSIG]) : AUGX_NINF; }
+        if (nUv > 0) { // the descriptors of the first block
+            const uint64_t uo = gp(gUdOff)[gb0 + bA];
+            const uint32_t uc = gp(gUdCnt)[gb0 + bA];
             if (t == 0) { (*lp(&L.uOff[0])) = uo; (*lp(&L.uCnt[0])) = uc; }
             const uint32_t words = (uc < (uint32_t)UDCAP ? uc : (uint32_t)UDCAP) * UDW;
             for (uint32_t i = (uint32_t)t; i < words; i += NT) (*lp(&L.ud[0][i])) = gp(gUd)[uo * UDW + i];
         }
     }
     BLOCK_SYNC();
+    // a finished cell to HBM.  A fix-up compares it first with what pass 1 left there: the offset of the tile, taken from the synch
+    // state at the end of the tile before, must hold for every cell (-inf == -inf counts; the back pointers carry no offset)
+    auto putCell = [&](int j, int s2, double f, int fa, bool bp) __attribute__((always_inline)) {
+        const int64_t at = (int64_t)j * S + s2;
+        if (over) {
+            if (cmp) {
+                const double old = ldCoherent(&M[at]);
+                if (!(f == old + ldsLoadD(&L.fxD))) (*lp(&L.fxBad)) = 1;
+                if (s2 == synch) (*lp(&L.fxDn)) = f - old;
+            }
+            gp(M)[at] = f;
+            if (bp && !FWD && BP) gp(BP)[at] = (uint8_t)fa;
+        } else if (f > AUGX_NINF) { gp(M)[at] = f; if (bp && !FWD && BP) gp(BP)[at] = (uint8_t)fa; }
+    };
     // what reaches chain slot `slot` at base jb + dj from the states that are not made in its own run
     // (acc: the other states are variable-length states whose cells of this block still sit in the accumulators -- the value of the
     //  base before is taken from there, as cellsOf makes it, so that this step need not wait for the cells)
@@ -1058,7 +1123,7 @@ AUGX_KFN void densePiece(const DevTables &T, const BatchView &B, DenseLds &L, in
             (*lp(&L.ring[j & 63][s2])) = f;
             // (near ties are being counted, dp.h: AUGX_NEAR_TIE: bit 6 of the back pointer says that the runner-up was that close)
             if (TIES && !FWD && fa < 8 && f2 > AUGX_NINF && f - f2 < B.nearTieEps) fa |= 0x40;
-            if (f > AUGX_NINF) { gp(M)[(int64_t)j * S + s2] = f; if (!FWD && BP) gp(BP)[(int64_t)j * S + s2] = (uint8_t)fa; }
+            putCell(j, s2, f, fa, true);
         }
     };
 #if !defined(AUGX_EMU) && defined(AUGX_PROFILE)
@@ -1085,7 +1150,7 @@ AUGX_KFN void densePiece(const DevTables &T, const BatchView &B, DenseLds &L, in
             }
             if (TIES && !FWD && fa < 8 && f2 > AUGX_NINF && f - f2 < B.nearTieEps) fa |= 0x40;
             (*lp(&L.ring[j & 63][s2])) = f;
-            if (f > AUGX_NINF) { gp(M)[(int64_t)j * S + s2] = f; if (!FWD && BP) gp(BP)[(int64_t)j * S + s2] = (uint8_t)fa; }
+            putCell(j, s2, f, fa, true);
             prev = f;
         }
     };
@@ -1101,7 +1166,7 @@ AUGX_KFN void densePiece(const DevTables &T, const BatchView &B, DenseLds &L, in
 #ifdef AUGX_EMU
     { bool general = false; for (int t = 0; t < nCh; t++) general = general || !cFast[t]; EDC(ED_CHAIN_GENERAL, general); EDC(ED_LATEACC_FALSE, !lateAcc); }
 #endif
-    for (int b = 0; b < nBlocks; b++) {
+    for (int b = bA; b < nBlocks; b++) {
         const int jb = b * BLK, par = b & 1;
         const int64_t gb = gb0 + b;
         DPROF(0);
@@ -1121,7 +1186,7 @@ AUGX_KFN void densePiece(const DevTables &T, const BatchView &B, DenseLds &L, in
                 fprintf(stderr, "emu: in-block predecessor of the late class that is of the late class itself: state %d kind %d j %d eop %d jb %d src %d\n", s2, T.kind[s2], jb + dj, eop, jb, (int)(I.src & 127u));
 #endif
             EDCALLER(0);
-            const double pv = denseAt<FWD>(L, M, S, eop, (int)(I.src & 127u), jb, BLK);
+            const double pv = denseAt<FWD>(L, M, S, eop, (int)(I.src & 127u), jb, BLK, jDead, synch);
 #ifdef AUGX_EMU // (AUGX_EMU_LATE_LOG=1: the live candidates of the late class that start from a cell of their own block, one line each)
             if (!FWD && eop >= jb && pv > AUGX_NINF && isLateKind(T, T.kind[s2]) && getenv("AUGX_EMU_LATE_LOG"))
                 fprintf(stderr, "emu: late in-block: state %d kind %d j %d eop %d jb %d src %d\n", s2, T.kind[s2], jb + dj, eop, jb, (int)(I.src & 127u));
@@ -1210,7 +1275,7 @@ AUGX_KFN void densePiece(const DevTables &T, const BatchView &B, DenseLds &L, in
                                 EDCALLER(1);
                                 _Pragma("unroll") for (int h = 0; h < UH; h++)
                                     _Pragma("unroll") for (int ai = 0; ai < 4; ai++)
-                                        pv[h][ai] = (act[h] && ai < na) ? denseAt<FWD>(L, M, S, eop[h], (*lp(&L.anc[s2][ai])), jb, BLK) : AUGX_NINF;
+                                        pv[h][ai] = (act[h] && ai < na) ? denseAt<FWD>(L, M, S, eop[h], (*lp(&L.anc[s2][ai])), jb, BLK, jDead, synch) : AUGX_NINF;
                                 // every candidate of the unit belongs to one cell: the lane combines its own (largest / sum), then one atomic
                                 double vmax = AUGX_NINF;
                                 unsigned long long vsum = 0ull;
@@ -1230,7 +1295,7 @@ AUGX_KFN void densePiece(const DevTables &T, const BatchView &B, DenseLds &L, in
                                         else vsum += (unsigned long long)(exp(v - cm) * FWD_FIX);
                                     }
                                     for (int ai = 4; ai < na; ai++) { // (no UTR exon state of the reference's models has more than four ancestors)
-                                        const double pw = denseAt<FWD>(L, M, S, eop[h], (*lp(&L.anc[s2][ai])), jb, BLK);
+                                        const double pw = denseAt<FWD>(L, M, S, eop[h], (*lp(&L.anc[s2][ai])), jb, BLK, jDead, synch);
                                         if (!(pw > AUGX_NINF)) continue;
                                         const double v = pw + (trn(cc, s2, ai) + te);
                                         if (!sumPass) vmax = v > vmax ? v : vmax;
@@ -1252,7 +1317,7 @@ AUGX_KFN void densePiece(const DevTables &T, const BatchView &B, DenseLds &L, in
                     double f = (*lp(&L.cmax[par][dj][s2]));
                     if (FWD) f = (*lp(&L.csum[par][dj][s2])) > 0ull ? f + log((double)(*lp(&L.csum[par][dj][s2])) / FWD_FIX) : AUGX_NINF;
                     (*lp(&L.ring[j & 63][s2])) = f;
-                    if (f > AUGX_NINF) gp(M)[(int64_t)j * S + s2] = f;
+                    putCell(j, s2, f, 0, false);
                 }
             }
         };
@@ -1286,7 +1351,7 @@ AUGX_KFN void densePiece(const DevTables &T, const BatchView &B, DenseLds &L, in
                         const int cc = clsAt(j), na = (*lp(&L.nanc[s2]));
                         for (int ai = 0; ai < na; ai++) {
                             EDCALLER(2);
-                            const double pv = denseAt<FWD>(L, M, S, j - lag, (*lp(&L.anc[s2][ai])), jb, BLK);
+                            const double pv = denseAt<FWD>(L, M, S, j - lag, (*lp(&L.anc[s2][ai])), jb, BLK, jDead, synch);
                             if (!(pv > AUGX_NINF)) continue;
                             const double x = pv + (trn(cc, s2, ai) + emi);
                             if (FWD) f = lse2(f, x);
@@ -1294,7 +1359,7 @@ AUGX_KFN void densePiece(const DevTables &T, const BatchView &B, DenseLds &L, in
                         }
                     }
                     (*lp(&L.ring[j & 63][s2])) = f;
-                    if (f > AUGX_NINF) { gp(M)[(int64_t)j * S + s2] = f; if (!FWD && BP) gp(BP)[(int64_t)j * S + s2] = (uint8_t)fa; }
+                    putCell(j, s2, f, fa, true);
                 }
             }
         }
@@ -1367,6 +1432,24 @@ AUGX_KFN void densePiece(const DevTables &T, const BatchView &B, DenseLds &L, in
         // the columns of this block reach HBM before any later block reads them from there (the ring covers 64 bases)
         if (((b + 1) * BLK) % 32 == 0) BLOCK_GLOBAL_SYNC();
         DPROF(10);
+        if (cmp && ((b + 1) * BLK) % WAVE == 0) { // a fix-up at the end of a tile: did it verify, with the offset of the tile before?
+            FOR_THREADS(t) {
+                if (t == 0) {
+                    const int tile = jb / WAVE;
+                    const double dNow = (*lp(&L.fxD)), dNext = (*lp(&L.fxDn));
+                    const int run = (!(*lp(&L.fxBad)) && dNow == dNext) ? (*lp(&L.fxRun)) + 1 : 0;
+                    (*lp(&L.fxRun)) = run; (*lp(&L.fxBad)) = 0; (*lp(&L.fxD)) = dNext;
+                    if (run >= B.segCheckTiles) { B.segStop[segQ] = tile; B.segD[segQ] = dNow; (*lp(&L.fxStop)) = 1; }
+                    else if (tile >= tlim) { B.segStop[segQ] = -2 - tile; B.segD[segQ] = 0.0; (*lp(&L.fxStop)) = 1; } // gave up: pass 3 goes on from here
+                }
+            }
+            BLOCK_SYNC();
+            if (uni((*lp(&L.fxStop)))) break; // (the same for every thread: read from LDS after the barrier)
+        }
+    }
+    if (SEG && (cmp || jE < n)) { // (not the run of the last tile; a fix-up always ends before it, SegDesc::tlim)
+        if (cmp) { FOR_THREADS(t) { if (t == 0 && !(*lp(&L.fxStop))) B.segStatus[segQ] = 1; } }
+        return;
     }
 #if !defined(AUGX_EMU) && defined(AUGX_PROFILE)
     if (B.prof && threadIdx.x == WAVE) for (int k = 0; k < 12; k++) B.prof[(int64_t)p * 56 + k] = dpAcc[k];
@@ -1385,8 +1468,21 @@ AUGX_KFN void densePiece(const DevTables &T, const BatchView &B, DenseLds &L, in
             }
             if (FWD) B.lnFwd[p] = tot;
             else { B.lnv[p] = tot; B.finalState[p] = fin; B.status[p] = fin < 0 ? AUGX_E_NOPATH : fabs(tot) < AUGX_EXACT_LIMIT ? 0 : AUGX_E_RANGE; }
+            if (SEG && pass == 3) { const int lastTile = (n + WAVE - 1) / WAVE - 1; B.segStop2[segQ] = lastTile; B.segD2[segQ] = 0.0; B.pieceCovered[p] = lastTile; }
         }
     }
+}
+#ifdef AUGX_EMU
+// (tests: an emulator library that decodes in segments sets this; true: it has decoded piece p, passes and finalize)
+static bool (*g_emuDenseSegHook)(const DevTables &, const BatchView &, DenseLds &, int p, int blk) = nullptr;
+#endif
+// the whole piece by one workgroup
+template <int BLK, int MODE, bool TIES = false> // TIES (MODE 0): the chain runs flag near ties (dp.h: AUGX_NEAR_TIE) -- a build of its own
+AUGX_KFN void densePiece(const DevTables &T, const BatchView &B, DenseLds &L, int p) {
+#ifdef AUGX_EMU
+    if (MODE == 0 && g_emuDenseSegHook && g_emuDenseSegHook(T, B, L, p, BLK)) return;
+#endif
+    denseTiles<BLK, MODE, TIES, 0>(T, B, L, p, 0);
 }
 
 // =================================================================================================
@@ -1406,6 +1502,8 @@ AUGX_KFN void denseBacktracePiece(const DevTables &T, const BatchView &B, int p)
     const int dssWhole = T.Ds + 2 + T.De, assLag = T.As + 2 + T.Ae + T.U;
     UCtx UX(T, B, p);
     auto colOf = [&](int eop) { return eop > 0 ? eop : 0; };
+    // a stored value in the true frame: candidates of one cell may begin in regions of different offsets (a piece decoded in segments)
+    auto cellAt = [&](int eop, int a) { const int q = colOf(eop); return M[(int64_t)q * S + a] + frameOff(B, p, q); };
     while (base > 0) {
         const int kind = T.kind[state];
         int eop, ai;
@@ -1468,7 +1566,7 @@ AUGX_KFN void denseBacktracePiece(const DevTables &T, const BatchView &B, int p)
                     double te; int e2;
                     if (c0 + l < D.total && utrCand(UX, D, c0 + l, te, e2))
                         for (int a2 = 0; a2 < T.n_anc[state]; a2++) { // (ascending, strict '>': the ancestor of lower index wins a tie)
-                            const double pv = M[(int64_t)colOf(e2) * S + T.anc[state][a2]];
+                            const double pv = cellAt(e2, T.anc[state][a2]);
                             if (!(pv > AUGX_NINF)) continue;
                             if (pass == 1 && e2 + KEY_BIAS == best.key && a2 == best.aux) continue; // (the winner itself)
                             const double v = pv + (lnT(T, cc, T.anc[state][a2], state) + te);
@@ -1504,7 +1602,7 @@ AUGX_KFN void denseBacktracePiece(const DevTables &T, const BatchView &B, int p)
                         const Item I = B.items[i0 + it];
                         if ((I.kp >> KEY_BITS) == pid && I.te > AUGX_NINF) {
                             const int e2 = (int)(I.kp & KEY_MASK) - KEY_BIAS, a = (int)(I.src & 127u);
-                            const double pv = M[(int64_t)colOf(e2) * S + a];
+                            const double pv = cellAt(e2, a);
                             if (pv > AUGX_NINF) {
                                 int a2 = 0;
                                 for (int i = 0; i < T.n_anc[state]; i++) if (T.anc[state][i] == a) a2 = i;

@@ -16,13 +16,16 @@ void launchForward(int blk, unsigned grid, hipStream_t st, const DevTables *T, c
 // kDense<BLK, MODE, TIES>, kUtrDesc<BLK> (k_dense.hip; dense.h: densePiece, utrDescGroup)
 void launchDense(int blk, int mode, bool ties, unsigned grid, hipStream_t st, const DevTables *T, const BatchView *B);
 void launchUtrDesc(int blk, unsigned grid, hipStream_t st, const DevTables *T, const BatchView &W);
+// kDenseSeg<BLK, TIES, PASS> (k_dense.hip; dense.h: denseTiles): pass 1 / 2 with one workgroup per segment, pass 3 with one per piece
+void launchDenseSeg(int blk, int pass, bool ties, unsigned grid, hipStream_t st, const DevTables *T, const BatchView *B);
 
 #define AUGX_DECL_TU(BLK_)                                                                                                     \
     void launchTrellis_##BLK_(int mode, bool ties, unsigned grid, hipStream_t st, const DevTables *T, const BatchView *B);     \
     void launchCand_##BLK_(bool multi, bool dense, unsigned grid, hipStream_t st, const DevTables *T, const BatchView &W);     \
     void launchForward_##BLK_(unsigned grid, hipStream_t st, const DevTables *T, const BatchView *B);                          \
     void launchDense_##BLK_(int mode, bool ties, unsigned grid, hipStream_t st, const DevTables *T, const BatchView *B);       \
-    void launchUtrDesc_##BLK_(unsigned grid, hipStream_t st, const DevTables *T, const BatchView &W);
+    void launchUtrDesc_##BLK_(unsigned grid, hipStream_t st, const DevTables *T, const BatchView &W);                         \
+    void launchDenseSeg_##BLK_(int pass, bool ties, unsigned grid, hipStream_t st, const DevTables *T, const BatchView *B);
 AUGX_DECL_TU(8) AUGX_DECL_TU(4) AUGX_DECL_TU(2)
 #undef AUGX_DECL_TU
 #define AUGX_TU_CAT2(a, b) a##b

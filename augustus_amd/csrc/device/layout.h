@@ -125,6 +125,34 @@ inline bool segmentsSupported(const augx_tables &t) {
     const int dL = t.d - 2 - t.De - t.As - 2 - t.U;
     return t.state_kind[t.synch_state] == AUGX_K_IGENIC && dL >= 4 * WAVE && t.reachable[t.synch_state];
 }
+// ---- the same for the dense kernels (dense.h: denseTiles).  The matrix is in HBM and a fix-up compares in place, so a cut needs
+// only a dead start that the true run converges to: the synch state must be the intergenic state, reachable, and the only
+// intergenic state -- with two (--genemodel=atleastone / exactlyone) a dead start cannot know whether a gene has been seen, and the
+// two intergenic columns never merge into one offset: such a model is never cut.
+inline bool modelIsDense(const augx_tables &t);
+inline bool denseSegmentsSupported(const augx_tables &t) {
+    int nIg = 0;
+    for (int s = 0; s < t.S; s++) nIg += t.state_kind[s] == AUGX_K_IGENIC;
+    return nIg == 1 && t.state_kind[t.synch_state] == AUGX_K_IGENIC && t.reachable[t.synch_state];
+}
+// the check length of a dense model covers the longest look-back of any dense state: the longest exon, intron or UTR exon (the
+// lengths forwardCellCandidates goes by, and the lag of the equalD states), the signal windows a state carries at either end, and the
+// 64 columns of the ring
+inline int denseSegCheckTiles(const augx_tables &t) {
+    int reach = t.max_exon_len > t.d ? t.max_exon_len : t.d;
+    const int dL = t.d - 2 - t.De - t.As - 2 - t.U;
+    if (dL > reach) reach = dL;
+    if (t.utr) {
+        if (t.utr_max_exon_len > reach) reach = t.utr_max_exon_len;
+        if (t.utr_max3single > reach) reach = t.utr_max3single;
+        if (t.utr_max3term > reach) reach = t.utr_max3term;
+        reach += t.tss_upwin + t.tss_end + t.aataaa_boxlen + t.d_polyasig_cleavage;
+    }
+    reach += t.W + t.U + (t.As + 2 + t.Ae) + (t.Ds + 2 + t.De) + 64;
+    return (reach + WAVE - 1) / WAVE + 2;
+}
+// can pieces of this model be cut, by whichever kernel family decodes it?
+inline bool modelSegmentable(const augx_tables &t) { return modelIsDense(t) ? denseSegmentsSupported(t) : segmentsSupported(t); }
 // Estimated length of pass 2 in tiles: `nFix` fix-ups on `slots` workgroups.  A round of concurrent fix-ups takes as long as its
 // longest one, and the length of a fix-up on random DNA has a heavy tail (CPU emulator, 176 fix-ups under the human model: mean
 // 374 tiles, median 348, p90 665, longest 1 122): the longest of n grows by about SEG_FIX_PER_BIT tiles per doubling of n.  A second
@@ -200,9 +228,13 @@ inline bool planRuns(const std::vector<int> &tiles, int slots, int minSeg, int h
 }
 // segTiles: tiles per segment wanted (0: choose so that `slots` workgroups are busy; < 0: never cut).  AUGX_SEG_LEN (bases)
 // overrides it (tests; 0 = never cut).
-inline SegPlan planSegments(const BatchLayout &L, const augx_tables &t, int slots, int segTiles = 0) {
+// A model of the dense kernels (decided here, so that every caller gets the plan the launches follow): by default its pieces are cut
+// only when the batch has fewer pieces than slots -- equal segments, none shorter than minSeg, at most `slots` in all, no runs; with at
+// least as many pieces as slots nothing is cut.  A piece without a nucleotide is never cut (`pieces`: the bases, where the caller has them).
+inline SegPlan planSegments(const BatchLayout &L, const augx_tables &t, int slots, int segTiles = 0, const augx_piece *pieces = nullptr) {
     SegPlan P;
-    P.checkTiles = segCheckTiles(t);
+    const bool dense = modelIsDense(t);
+    P.checkTiles = dense ? denseSegCheckTiles(t) : segCheckTiles(t);
     const int n = L.nPieces;
     if (const char *e = getenv("AUGX_SEG_LEN")) { const long v = atol(e); segTiles = v <= 0 ? -1 : (int)((v + WAVE - 1) / WAVE); }
     const int minSeg = 5 * P.checkTiles; // a segment holds its own fix-up (convergence + checkTiles) and the look-back of the next one
@@ -213,7 +245,17 @@ inline SegPlan planSegments(const BatchLayout &L, const augx_tables &t, int slot
     int64_t total = 0;
     int maxTiles = 0;
     for (int p = 0; p < n; p++) { tiles[p] = (L.len[p] + WAVE - 1) / WAVE; total += tiles[p]; if (tiles[p] > maxTiles) maxTiles = tiles[p]; }
-    if (!segmentsSupported(t)) segTiles = -1;
+    if (!(dense ? denseSegmentsSupported(t) : segmentsSupported(t))) segTiles = -1;
+    std::vector<char> whole(n, 0); // pieces that stay in one segment whatever the plan
+    if (dense && pieces && segTiles >= 0)
+        for (int p = 0; p < n; p++) {
+            if (!pieces[p].seq) continue;
+            bool nuc = false;
+            for (int64_t q = 0; q < pieces[p].len && !nuc; q++) { const char c = (char)(pieces[p].seq[q] | 0x20); nuc = c == 'a' || c == 'c' || c == 'g' || c == 't'; }
+            whole[p] = !nuc;
+        }
+    bool denseDefault = false;
+    if (dense && segTiles == 0) { if (n < slots) denseDefault = true; else segTiles = -1; }
     auto countFor = [&](int st, int p) { // nearest count, no segment shorter than minSeg
         int k = (tiles[p] + st / 2) / st;
         while (k > 1 && tiles[p] / k < minSeg) k--;
@@ -221,7 +263,7 @@ inline SegPlan planSegments(const BatchLayout &L, const augx_tables &t, int slot
     };
     RunCuts R;
     bool useRuns = false;
-    if (segTiles == 0) {
+    if (segTiles == 0 && !denseDefault) {
         // estimate of the time of the three passes for a candidate plan, in tiles.  Pieces cut one by one: rounds of `slots`
         // concurrent workgroups (the hardware hands out the segments as compute units fall free), each as long as the longest
         // segment; then the fix-ups (segFixTiles)
@@ -280,7 +322,10 @@ inline SegPlan planSegments(const BatchLayout &L, const augx_tables &t, int slot
     }
     if (segTiles > 0 && segTiles < minSeg) segTiles = minSeg;
     std::vector<int> kOf(n, 1);
-    if (segTiles > 0) {
+    if (denseDefault) { // every piece its share of the slots
+        const int share = slots / n;
+        for (int p = 0; p < n; p++) { const int k = tiles[p] / minSeg; kOf[p] = whole[p] || k < 1 ? 1 : k < share ? k : share; }
+    } else if (segTiles > 0) {
         int64_t nSeg = 0;
         for (int p = 0; p < n; p++) { kOf[p] = countFor(segTiles, p); nSeg += kOf[p]; }
         // whole rounds: when the segments nearly fill a last round of `slots` workgroups, a few pieces get one segment more
@@ -289,6 +334,7 @@ inline SegPlan planSegments(const BatchLayout &L, const augx_tables &t, int slot
         if (extra > 0 && extra <= n / 4 + 1)
             for (int p = 0; p < n && extra > 0; p++)
                 if (kOf[p] > 1 && tiles[p] / (kOf[p] + 1) >= minSeg) { kOf[p]++; extra--; }
+        for (int p = 0; p < n; p++) if (whole[p]) kOf[p] = 1;
     }
     for (int p = 0; p < n; p++) {
         const int kp = kOf[p];

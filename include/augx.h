@@ -324,6 +324,12 @@ int augx_plan_segments(const augx_tables *t, const int64_t *lens, int n, int slo
                        int32_t *run_seg0 /* [cap_runs + 1] */, int cap_runs, int *n_runs, int *check_tiles, int64_t *est /* [2] */);
 int augx_batch_plan(augx_decoder *d, augx_batch *b, int32_t *segs, int cap_segs, int *n_segs, int32_t *run_seg0, int cap_runs, int *n_runs,
                     int *check_tiles, int64_t *est, int32_t *seg_stop /* [cap_segs] */, int32_t *seg_stop2 /* [cap_segs] */);
+/* Both kernel families cut pieces: the 47-state trellis kernels, and the dense kernels (models with UTR states, and the 47-state
+ * models whose windows the trellis layout refuses), whose default plan cuts only a batch with fewer pieces than workgroup slots (equal
+ * segments, no runs) and never a piece without a nucleotide.  Never cut: the forward pass (its ln-sums are not exact), and the models
+ * with two intergenic states (--genemodel=atleastone / exactlyone: a dead start cannot know whether a gene has been seen).
+ * augx_model_segmentable: 1 when pieces of the model can be cut, by whichever family decodes it, 0 otherwise */
+int augx_model_segmentable(const augx_tables *t);
 /* How a model is laid out on the device, without a device: out[0] kernel family (0 trellis, 1 dense), out[1] block size (8, 4 or 2;
  * AUGX_BLK in the environment applies), out[2] 1 where the candidates of the initial exon states are in the late class of the dense
  * kernels -- models whose trans_init_window leaves the shortest initial exon state less than one block (schistosoma, galdieria,
